@@ -16,12 +16,19 @@ the time.
 Shards come from lcb_hash_partition (include/lcb_hash_gpu.h), the library's
 own work-balanced split.  `--gpus N` without a torch.distributed launcher
 starts the N ranks itself (a torch.distributed.run child, before any GPU
-call); under a launcher WORLD_SIZE must equal N.  After timing, the ranks'
-digests are gathered to rank 0 over RCCL (timed separately, never part of
-`value`) and checked against the reference's digest-of-digests
-(tests/golden/batches.json C3, tests/golden/large.json C5).
+call); under a launcher WORLD_SIZE must equal N.
 
-Extra fields on the JSON line:
+A plain run sets up, warms up, times the steps and prints the result line
+(headline, its roofline from the timed launches and the committed counters).
+`--dump-outputs DIR` also writes the digests the last timed step produced
+(DIR/digests.npy, float32, a fixed seeded sample of rows when large; the
+inputs are the same seeded stream in every run).  Everything else runs only
+with `--full`: after timing, the ranks' digests are gathered to rank 0 over
+RCCL (timed separately, never part of `value`) and checked against the
+reference's digest-of-digests (tests/golden/batches.json C3,
+tests/golden/large.json C5), followed by the measurements below.
+
+Extra fields on the JSON line (`--full`, except roofline):
   roofline      dominant kernel vs HBM peak (algorithmic bytes / HIP-event
                 kernel time); traffic from a committed rocprofv3 PMC summary
                 (profiles/pmc_<alg>.json) when one exists for this workload;
@@ -76,9 +83,15 @@ def parse(argv=None):
     p.add_argument("--count", type=int, default=MSGS_PER_GPU, help="buffers per GPU (weak scaling)")
     p.add_argument("--global-count", type=int, default=8 * MSGS_PER_GPU,
                    help="buffers of the whole job (strong scaling)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
-    p.add_argument("--no-extras", action="store_true", help="skip per_alg / e2e")
-    p.add_argument("--no-gather", action="store_true", help="skip the RCCL digest gather + fixture check")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run everything else: read probes, digest gather + fixture "
+                        "check, per_alg / hmac / ragged / crc32 / chacha / ingest / e2e and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the digests of the last timed step to DIR/<name>.npy (float32)")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip per_alg / e2e")
+    p.add_argument("--no-gather", action="store_true",
+                   help="with --full: skip the RCCL digest gather + fixture check")
     p.add_argument("--cpu-threads", type=int, default=0)
     p.add_argument("--settle", default="gen", choices=("self", "gen"),
                    help="headline warm-up: the synthetic-stream generator (default) or the measured kernel itself")
@@ -314,6 +327,29 @@ def time_alg(alg, data, digests, count, steps, warmup, world, key=None):
     span = e0.elapsed_time(e1)
     kms = span / steps
     return max_over_ranks(t, world), kms, cw.result(span)
+
+
+DUMP_BYTES = 32 << 20     # float32 bytes of digests per rank that --dump-outputs writes
+
+
+def dump_outputs(path, digests, count, rank, world):
+    """--dump-outputs: what the last timed step left in the caller's digest
+    buffer (count x D bytes), one float32 per digest byte, as
+    <path>/digests.npy (digests_rank<r>.npy when there are several ranks).
+    At most DUMP_BYTES: of a larger output a fixed sample of rows (seeded,
+    ascending; the same rows in every run of the same arguments), whose
+    shard-relative indices go to digests_rows.npy (float64) beside it."""
+    os.makedirs(path, exist_ok=True)
+    D = digests.shape[1]
+    keep = min(count, DUMP_BYTES // (4 * D))
+    rows = np.arange(count, dtype=np.int64)
+    if keep < count:
+        rows = np.sort(np.random.default_rng(SEED % (1 << 32)).choice(count, keep, replace=False))
+    torch.cuda.synchronize()
+    got = digests[torch.as_tensor(rows, device=digests.device)].cpu().numpy()
+    sfx = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(path, "digests%s.npy" % sfx), got.astype(np.float32))
+    np.save(os.path.join(path, "digests_rows%s.npy" % sfx), rows.astype(np.float64))
 
 
 def counters_current(rec):
@@ -987,6 +1023,8 @@ def main():
     sp = torch.cuda.current_stream().cuda_stream
     settle(launch=(lambda: check(hash_launch(alg, data, digests, count, sp))) if a.settle == "self" else None)
     t, kms, clock = time_alg(alg, data, digests, count, a.steps, a.warmup, world)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, digests, count, rank, world)
     value = total * MSG_LEN * a.steps / t / 2**30
     alg_bytes = count * (MSG_LEN + D)      # read every message once + write its digest
     achieved = alg_bytes / (kms * 1e-3) / 1e9
@@ -1040,7 +1078,7 @@ def main():
     # of them above 1 -- VERDICT r5.  The floor is now taken at the clock of
     # the timed launches themselves, `clock` above.)
 
-    if rank == 0 and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_extras:
         # Achievable read rate on this box next to the spec peak: the same
         # records through the kernel's line stream without compression, and a
         # plain linear read (not `value`; the fraction against spec stays `frac`).
@@ -1050,7 +1088,7 @@ def main():
         r["frac_of_stream"] = round(achieved / pr["records_GBps"], 4)
         r["frac_of_linear_read"] = round(achieved / pr["linear_GBps"], 4)
 
-    if not a.no_gather:
+    if a.full and not a.no_gather:
         # RCCL digest gather to rank 0 (outside the timed region), then the
         # whole job's digests against the reference's digest-of-digests.
         allg, gms = gather_digests(digests[:count], first, count, total, world, rank)
@@ -1063,7 +1101,7 @@ def main():
             out.setdefault("verify", {})["job_digests_equal_reference"] = ok
             out["verify"]["digest_of_digests"] = got
 
-    if rank == 0 and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_extras:
         settle()
         per = {}
         for name, aid in sorted(ALG_IDS.items(), key=lambda x: x[1]):
@@ -1194,7 +1232,7 @@ def main():
         gpu_dig = digests.cpu().numpy()
         out.setdefault("verify", {})["e2e_equals_device"] = bool(np.array_equal(hd, gpu_dig))
 
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         threads = a.cpu_threads or host_threads()
         best, res, one, t16, taff, cdata = cpu_baseline(alg, count, threads)
         gbs, tcpu, dcpu, reps = res[best]

@@ -43,7 +43,7 @@ def _check_shards(j, total):
 
 def test_bench_two_ranks_gloo_one_gpu():
     j, ndev = _run_bench(["--gpus", "2", "--dist-backend", "gloo", "--steps", "5", "--warmup", "2",
-                          "--no-extras", "--no-cpu"], 240)
+                          "--full", "--no-extras", "--no-cpu"], 240)
     assert j["world_size"] == 2 and j["dist_backend"] == "gloo"
     # the physical devices used, not the rank count (ranks share a 1-GPU box)
     assert j["n_gpus"] == min(2, ndev) and j["ranks_share_devices"] == (ndev < 2)
@@ -56,7 +56,7 @@ def test_bench_two_ranks_gloo_one_gpu():
 def test_bench_eight_ranks_strong_c5_one_gpu():
     """C5 (BASELINE configs[4]): 8M x 1 KiB split over 8 ranks, strong scaling."""
     j, ndev = _run_bench(["--gpus", "8", "--dist-backend", "gloo", "--scaling", "strong", "--steps", "3",
-                          "--warmup", "1", "--no-extras", "--no-cpu"], 420)
+                          "--warmup", "1", "--full", "--no-extras", "--no-cpu"], 420)
     assert j["world_size"] == 8 and j["scaling"] == "strong"
     assert j["n_gpus"] == min(8, ndev) and j["ranks_share_devices"] == (ndev < 8)
     _check_shards(j, 8 << 20)
