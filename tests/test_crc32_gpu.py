@@ -135,6 +135,67 @@ def test_host_mode_pinned_and_chained(gpu, oracle):
         assert np.array_equal(second, whole), v
 
 
+def _dev_view(host, base):
+    """`host` on the device at `base` bytes past a 128-B aligned address."""
+    full = torch.zeros(base + host.size + 16, dtype=torch.uint8, device="cuda")
+    view = full[base:base + host.size]
+    view.copy_(torch.from_numpy(host))
+    assert view.data_ptr() % 128 == base
+    return view
+
+
+FIXED_LAYOUTS = [
+    pytest.param(256, 256, 0, id="256x256-lds-nt-policy"),
+    pytest.param(272, 200, 0, id="272x200-lds-gather-72B-tail"),
+    pytest.param(144, 129, 0, id="144x129-lds-gather-1B-tail"),
+    pytest.param(256, 256, 16, id="256x256-base+16-lds-gather"),
+    pytest.param(256, 256, 4, id="256x256-base+4-per-lane-kernel"),
+]
+
+
+@pytest.mark.parametrize("stride,flen,base", FIXED_LAYOUTS)
+@pytest.mark.parametrize("v", sorted(CRC_VARIANTS), ids=lambda v: CRC_VARIANTS[v])
+def test_fixed_stride_paths_vs_oracle(gpu, oracle, v, stride, flen, base):
+    """crc_fixed_lds_kernel under both cache policies (stride and base 128-B
+    aligned or not), with a tail through crc_message, a full wave (64), a
+    one-record partial last wave (65) and 4 waves + 44 (300), one-shot and
+    with per-record init (X_update); base + 4 leaves fixed_stride_lines for
+    the per-lane kernel.  All 8 variants: both lookup rules, every init /
+    final inversion."""
+    from liblcb_amd.crc32 import crc32_batch
+    rng = np.random.default_rng([v, stride, flen, base])
+    for count in (64, 65, 300):
+        host = rng.integers(0, 256, count * stride, dtype=np.uint8)
+        data = _dev_view(host, base)
+        init = rng.integers(0, 1 << 32, count, dtype=np.uint64).astype(np.uint32)
+        for ini in (None, init):
+            out = crc32_batch(v, data, count=count, stride=stride, fixed_len=flen,
+                              init=dev(ini.astype(np.int32)) if ini is not None else None)
+            torch.cuda.synchronize()
+            exp = oracle.crc32_batch(v, host, count=count, stride=stride, fixed_len=flen, init=ini)
+            assert np.array_equal(out.cpu().numpy().view(np.uint32), exp), (count, ini is not None)
+
+
+@pytest.mark.parametrize("stride,flen", [pytest.param(256, 256, id="256x256-nt-one-line-after-init"),
+                                         pytest.param(400, 330, id="400x330-gather-line+74B-after-init")])
+@pytest.mark.parametrize("v", sorted(CRC_VARIANTS), ids=lambda v: CRC_VARIANTS[v])
+def test_chained_init_on_lds_kernel(gpu, oracle, v, stride, flen):
+    """X(first 128 B) fed as init to the remaining fixed_len - 128 bytes of a
+    fixed-stride layout (>= 128 B, so init reaches crc_fixed_lds_kernel)
+    equals the one-shot CRC; 300 records = 4 waves + a partial one."""
+    from liblcb_amd.crc32 import crc32_batch
+    count = 300
+    host = np.random.default_rng([v, stride]).integers(0, 256, count * stride, dtype=np.uint8)
+    data = _dev_view(host, 0)
+    first = crc32_batch(v, data, count=count, stride=stride, fixed_len=128)
+    second = crc32_batch(v, data[128:], count=count, stride=stride, fixed_len=flen - 128, init=first)
+    whole = crc32_batch(v, data, count=count, stride=stride, fixed_len=flen)
+    torch.cuda.synchronize()
+    exp = oracle.crc32_batch(v, host, count=count, stride=stride, fixed_len=flen)
+    assert np.array_equal(whole.cpu().numpy().view(np.uint32), exp)
+    assert np.array_equal(second.cpu().numpy().view(np.uint32), exp)
+
+
 def test_named_entry_points(gpu, oracle):
     import liblcb_amd.crc32 as c
     msg = np.frombuffer(b"123456789", np.uint8)
