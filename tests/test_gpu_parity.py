@@ -682,33 +682,49 @@ def test_gost_segmented_mixed_lengths(gpu, alg, monkeypatch):
     torch.cuda.empty_cache()
 
 
+def _ragged_batch(seed, lens):
+    rng = np.random.default_rng(seed)
+    offs = np.zeros(len(lens), np.uint64)
+    offs[1:] = np.cumsum(lens[:-1].astype(np.uint64) + rng.integers(0, 16, len(lens) - 1).astype(np.uint64))
+    return gen_stream(seed, int(offs[-1] + lens[-1]) + 64), offs, lens
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("alg", [1, 6])
-def test_bucketing_one_kernel_form(gpu, alg, monkeypatch):
-    """The one-kernel bucketing (LCB_BUCKET_FUSED=1, lcb_kernels.hip
-    bucket_fused_kernel: ticket-ordered count and place phases) gives the
-    same digests as the default three-kernel form: the 1M-packet layout
-    (tile kernel, padded runs; MD5) and a 300K-message mix with segmented
-    long waves (SHA-512, unpadded), three passes each (its sync words reset
-    between uses), and a keyed batch (the fused key-index check)."""
-    from tests.golden_util import packet_layout
-    offs, lens, total = packet_layout()
-    data = gpu.gen_synthetic(0xB0C, total)
-    do = torch.as_tensor(offs.astype(np.int64), device="cuda")
-    dl = torch.as_tensor(lens.astype(np.int32), device="cuda")
-    ref = gpu.hash_batch(alg, data, offsets=do, lengths=dl).cpu().numpy()
-    monkeypatch.setenv("LCB_BUCKET_FUSED", "1")
-    for rep in range(3):
-        got = gpu.hash_batch(alg, data, offsets=do, lengths=dl).cpu().numpy()
-        assert np.array_equal(got, ref), (alg, rep)
-    kidx = torch.as_tensor((np.arange(len(lens)) % 5).astype(np.int32), device="cuda")
-    keys = [bytes([k]) * (7 * k + 1) for k in range(5)]
-    kf = gpu.hash_batch_keyed(alg, 1, keys, data, key_index=kidx, offsets=do, lengths=dl).cpu().numpy()
-    monkeypatch.delenv("LCB_BUCKET_FUSED")
-    kr = gpu.hash_batch_keyed(alg, 1, keys, data, key_index=kidx, offsets=do, lengths=dl).cpu().numpy()
-    assert np.array_equal(kf, kr), alg
-    del data
-    torch.cuda.empty_cache()
+@pytest.mark.parametrize("alg,keyed", [(1, False), (6, False), (1, True)])
+def test_bucketing_dirty_scratch(gpu, oracle, alg, keyed):
+    """A bucketed batch is right whatever its scratch held before: the three
+    bucketing kernels write every word they or the batch kernel read, and
+    nothing zeroes the scratch between batches.  Three batches back to back
+    on one stream (no synchronise in between; they share the stream's scratch
+    buffer, 1 MiB at least), every digest against the oracle:
+      A  12,289 messages of 0..4159 bytes at byte gaps 0..15: 4 bucketing
+         blocks, 256 keys (64 classes x 4 phases), unpadded runs;
+      B  8,193 messages of 7 or 70 bytes: at most 8 keys, 8,193 >= 16 x 64 x 8,
+         so in the tile form every run is padded and kOrderPad entries land
+         where A's `order` lay;
+      A  again, over B's leftovers.
+    Batch kernels (tiles_take; all counts are below md_lines_kernel's
+    16,384): MD5 -> md_tiles_kernel, plain; SHA-512 -> md_batch_kernel over
+    the unpadded order; MD5 keyed HMAC (5 keys, key i % 5) -> md_tiles_kernel,
+    keyed HMAC, with bucket_count_kernel<true> checking the key indices."""
+    rng = np.random.default_rng(0xD127)
+    A = _ragged_batch(0xD1A, rng.integers(0, 4160, 12289).astype(np.uint32))
+    B = _ragged_batch(0xD1B, rng.choice(np.array([7, 70], np.uint32), 8193))
+    keys = [bytes([k + 1]) * (7 * k + 1) for k in range(5)]
+    up = [(dev(data), dev(offs, np.int64), dev(lens, np.int32), dev(np.arange(len(lens)) % 5, np.int32))
+          for data, offs, lens in (A, B)]
+    got = []
+    for dd, do, dl, dk in (up[0], up[1], up[0]):
+        if keyed:
+            got.append(gpu.hash_batch_keyed(alg, 1, keys, dd, key_index=dk, offsets=do, lengths=dl))
+        else:
+            got.append(gpu.hash_batch(alg, dd, offsets=do, lengths=dl))
+    for j, (data, offs, lens) in enumerate((A, B, A)):
+        if keyed:
+            exp = oracle.batch_keyed(alg, 1, keys, data, np.arange(len(lens)) % 5, offs, lens)
+        else:
+            exp = oracle.batch(alg, data, offs, lens)
+        assert np.array_equal(got[j].cpu().numpy(), exp), (alg, keyed, "ABA"[j])
 
 
 @pytest.mark.gpu

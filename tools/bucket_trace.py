@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Median durations of the bucketing kernels (and the batch kernel after
-them) in a rocprofv3 --kernel-trace rocpd database of tools/bucket_ab.py.
+them) in a rocprofv3 --kernel-trace rocpd database of any run with bucketed
+batches (tools/env_ab.py, tools/pkt_bench.py, bench.py).
 
 usage: python3 tools/bucket_trace.py <results.db>"""
 import re

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-process A/B of a library environment switch read per call (e.g.
-LCB_BUCKET_CHUNK=8192 against unset) on the 1M-packet MD5 pass (bench
+LCB_TILE_SEGS=0 against unset) on the 1M-packet MD5 pass (bench
 ragged_packets shape): alternating rounds, mean HIP-event ms per pass, the
 digests of both settings compared.  A kernel trace of the same command
 (rocprofv3 --kernel-trace) gives the bucketing kernels' own durations
