@@ -4,14 +4,17 @@ The product is the C-ABI library liblcb_hash_gpu.so (include/lcb_hash_gpu.h,
 HIP kernels in csrc/).  This package is its host-side Python mirror of the
 reference's one-shot API (liblcb_amd.hash), the CRC-32 family of
 include/math/crc32.h (liblcb_amd.crc32), the ChaCha / XChaCha cipher of
-include/crypto/cipher/chacha.h (liblcb_amd.chacha), the asynchronous
+include/crypto/cipher/chacha.h (liblcb_amd.chacha), the GOST 28147-89 block
+cipher and MAC of include/crypto/cipher/gost28147.h (liblcb_amd.gost28147,
+its own library liblcb_gost28147_gpu.so), the asynchronous
 packet ingestion queue (liblcb_amd.queue) and batched RADIUS packet
 signing / verification over the keyed batches (liblcb_amd.radius).
 """
 from ._lib import (ALG_IDS, ALG_NAMES, BLOCK_SIZE, DIGEST_SIZE, GOST256, GOST512, MD5, SHA1,
                    SHA224, SHA256, SHA384, SHA512, LcbHashError, lib)
 from .hash import *  # noqa: F401,F403
-from . import chacha, crc32, queue, radius  # noqa: F401,E402  (cipher, CRC-32, ingestion queue, RADIUS)
+from . import chacha, crc32, gost28147, queue, radius  # noqa: F401,E402  (ciphers, CRC-32, ingestion queue, RADIUS)
+from .gost28147 import gost28147_lib  # noqa: F401,E402
 
 __all__ = ["ALG_IDS", "ALG_NAMES", "BLOCK_SIZE", "DIGEST_SIZE", "MD5", "SHA1", "SHA224",
-           "SHA256", "SHA384", "SHA512", "GOST256", "GOST512", "LcbHashError", "lib"]
+           "SHA256", "SHA384", "SHA512", "GOST256", "GOST512", "LcbHashError", "lib", "gost28147_lib"]
