@@ -8,13 +8,16 @@ include/crypto/cipher/chacha.h (liblcb_amd.chacha), the GOST 28147-89 block
 cipher and MAC of include/crypto/cipher/gost28147.h (liblcb_amd.gost28147,
 its own library liblcb_gost28147_gpu.so), the asynchronous
 packet ingestion queue (liblcb_amd.queue) and batched RADIUS packet
-signing / verification over the keyed batches (liblcb_amd.radius).
+signing / verification: per packet over the keyed batches with the packet
+logic on the host (liblcb_amd.radius) and packed, wholly on the device
+(liblcb_amd.radius_batch, its own library liblcb_radius_gpu.so).
 """
 from ._lib import (ALG_IDS, ALG_NAMES, BLOCK_SIZE, DIGEST_SIZE, GOST256, GOST512, MD5, SHA1,
                    SHA224, SHA256, SHA384, SHA512, LcbHashError, lib)
 from .hash import *  # noqa: F401,F403
-from . import chacha, crc32, gost28147, queue, radius  # noqa: F401,E402  (ciphers, CRC-32, ingestion queue, RADIUS)
+from . import chacha, crc32, gost28147, queue, radius, radius_batch  # noqa: F401,E402  (ciphers, CRC-32, ingestion queue, RADIUS)
 from .gost28147 import gost28147_lib  # noqa: F401,E402
+from .radius_batch import radius_lib  # noqa: F401,E402
 
 __all__ = ["ALG_IDS", "ALG_NAMES", "BLOCK_SIZE", "DIGEST_SIZE", "MD5", "SHA1", "SHA224",
-           "SHA256", "SHA384", "SHA512", "GOST256", "GOST512", "LcbHashError", "lib", "gost28147_lib"]
+           "SHA256", "SHA384", "SHA512", "GOST256", "GOST512", "LcbHashError", "lib", "gost28147_lib", "radius_lib"]
