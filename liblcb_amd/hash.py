@@ -308,37 +308,92 @@ def multi_stats():
     return {n: int(getattr(st, n)) for n, _ in MultiStats._fields_}
 
 
+def _key_table(keys, key_table=None):
+    """The host key table of a keyed call -> (blob, key_offsets or None,
+    key_lengths, nkeys) as the C-ABI reads them (uint8 / uint64 / uint32).
+
+    keys       sequence of bytes, packed back to back; or
+    key_table  (blob, key_offsets or None, key_lengths), the caller's own
+               geometry (include/lcb_hash_gpu.h: any key_offsets[k] -- gaps,
+               any order, overlap; None: every key starts at blob[0]).  blob:
+               bytes or a uint8 numpy array, key_offsets int64 / uint64,
+               key_lengths int32 / uint32 numpy arrays (the dtypes are
+               checked, not converted: the C-ABI reads them as they are), as
+               many offsets as lengths, every key inside the blob.
+    Exactly one of the two is given."""
+    if (keys is None) == (key_table is None):
+        raise ValueError("give the keys as a list (keys) or as key_table=(blob, key_offsets, key_lengths), not both")
+    if key_table is None:
+        keys = [bytes(k) for k in keys]
+        blob = np.frombuffer(b"".join(keys) or b"\0", np.uint8)
+        klen = np.array([len(k) for k in keys], np.uint32)
+        koff = np.zeros(len(keys), np.uint64)
+        if len(keys) > 1:
+            koff[1:] = np.cumsum(klen[:-1], dtype=np.uint64)
+        return blob, koff, klen, len(keys)
+    try:
+        blob, koff, klen = key_table
+    except (TypeError, ValueError):
+        raise TypeError("key_table must be (blob, key_offsets or None, key_lengths)")
+    if isinstance(blob, (bytes, bytearray, memoryview)):
+        blob = np.frombuffer(bytes(blob), np.uint8)
+    for name, t, dts in (("key_table blob", blob, (np.uint8,)), ("key_offsets", koff, (np.int64, np.uint64)),
+                         ("key_lengths", klen, (np.int32, np.uint32))):
+        if t is None and name == "key_offsets":
+            continue
+        if not isinstance(t, np.ndarray) or t.dtype not in dts or t.ndim != 1 or not t.flags.c_contiguous:
+            raise TypeError("%s must be a contiguous 1-d numpy array of %s"
+                            % (name, " / ".join(np.dtype(d).name for d in dts)))
+    nkeys = int(klen.size)
+    if nkeys == 0:
+        raise ValueError("key_table holds no key")
+    if koff is not None and int(koff.size) != nkeys:
+        raise ValueError("key_offsets has %d entries, key_lengths %d" % (int(koff.size), nkeys))
+    if (klen.dtype == np.int32 and int(klen.min()) < 0) or \
+            (koff is not None and koff.dtype == np.int64 and int(koff.min()) < 0):
+        raise ValueError("negative key offset or length")
+    size = np.uint64(blob.size)
+    start = np.minimum(koff.astype(np.uint64), size) if koff is not None else np.zeros(nkeys, np.uint64)
+    out = klen.astype(np.uint64) > size - start        # no offset + length: a sum near 2^64 would wrap
+    if koff is not None:
+        out |= koff.astype(np.uint64) > size
+    if out.any():
+        k = int(out.argmax())
+        raise ValueError("key %d (offset %d, %d bytes) extends past the %d-byte key blob"
+                         % (k, int(koff[k]) if koff is not None else 0, int(klen[k]), int(blob.size)))
+    if blob.size == 0:
+        blob = np.zeros(1, np.uint8)
+    return blob, koff, klen, nkeys
+
+
 def hash_batch_keyed(alg, mode, keys, data, *, key_index=None, offsets=None, lengths=None, count=None,
-                     stride=None, fixed_len=None, out=None):
+                     stride=None, fixed_len=None, out=None, key_table=None):
     """lcb_hash_batch_keyed: message i hashed with key keys[key_index[i]]
     (key 0 without key_index) as HMAC(K, m) (KEY_HMAC), H(K || m)
     (KEY_PREFIX) or H(m || K) (KEY_SUFFIX) — the RADIUS shapes
-    (include/proto/radius.h:745-919, 1315-1377).  keys: sequence of bytes.
+    (include/proto/radius.h:745-919, 1315-1377).  keys: sequence of bytes, or
+    None with key_table=(blob, key_offsets or None, key_lengths) (_key_table).
     key_index lives with the batch: a device tensor in device mode."""
     if isinstance(alg, str):
         alg = ALG_IDS[alg]
     D = DIGEST_SIZE[alg]
-    keys = [bytes(k) for k in keys]
-    blob = np.frombuffer(b"".join(keys) or b"\0", np.uint8)
-    klen = np.array([len(k) for k in keys], np.uint32)
-    koff = np.zeros(len(keys), np.uint64)
-    if len(keys) > 1:
-        koff[1:] = np.cumsum(klen[:-1], dtype=np.uint64)
+    blob, koff, klen, nkeys = _key_table(keys, key_table)
+    koff_p = koff.ctypes.data if koff is not None else None
     L = lib()
     if _is_dev(data):
         count, stride, fixed_len, out = _dev_batch(data, count, offsets, lengths, stride, fixed_len, out, D,
                                                    per_msg=(("key_index", key_index),))
         with torch.cuda.device(data.device):
             stream = torch.cuda.current_stream(data.device).cuda_stream
-            check(L.lcb_hash_batch_keyed(alg, mode, blob.ctypes.data, koff.ctypes.data, klen.ctypes.data,
-                                         len(keys), key_index.data_ptr() if key_index is not None else None,
+            check(L.lcb_hash_batch_keyed(alg, mode, blob.ctypes.data, koff_p, klen.ctypes.data,
+                                         nkeys, key_index.data_ptr() if key_index is not None else None,
                                          data.data_ptr(), offsets.data_ptr() if offsets is not None else None,
                                          lengths.data_ptr() if lengths is not None else None,
                                          count, stride, fixed_len, out.data_ptr(), F_DEVICE, stream))
         return out
     data, offsets, lengths, (key_index,), count, stride, fixed_len, out, _ = _host_batch(
         data, count, offsets, lengths, stride, fixed_len, out, D, per_msg=(("key_index", key_index),))
-    check(L.lcb_hash_batch_keyed(alg, mode, blob.ctypes.data, koff.ctypes.data, klen.ctypes.data, len(keys),
+    check(L.lcb_hash_batch_keyed(alg, mode, blob.ctypes.data, koff_p, klen.ctypes.data, nkeys,
                                  key_index.ctypes.data if key_index is not None else None, data.ctypes.data,
                                  offsets.ctypes.data if offsets is not None else None,
                                  lengths.ctypes.data if lengths is not None else None,

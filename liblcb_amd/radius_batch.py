@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from ._lib import F_DEVICE, HERE, LcbHashError, c_sz, c_u32, c_u64, c_vp, check, lib
-from .hash import _dev_batch, _host_batch, _is_dev
+from .hash import _dev_batch, _host_batch, _is_dev, _key_table
 
 __all__ = ["radius_lib", "sign_packed", "verify_packed", "pack", "unpack", "req_headers", "RADIUS_SIGNATURES"]
 
@@ -90,25 +90,15 @@ def req_headers(requests):
     return out.reshape(-1)
 
 
-def _key_table(keys):
-    keys = [bytes(k) for k in keys]
-    blob = np.frombuffer(b"".join(keys) or b"\0", np.uint8)
-    klen = np.array([len(k) for k in keys], np.uint32)
-    koff = np.zeros(len(keys), np.uint64)
-    if len(keys) > 1:
-        koff[1:] = np.cumsum(klen[:-1], dtype=np.uint64)
-    return blob, koff, klen
-
-
 def _ptr(t):
     if t is None:
         return None
     return t.data_ptr() if isinstance(t, torch.Tensor) else t.ctypes.data
 
 
-def _run(verify, pkts, keys, key_index, offsets, buf_sizes, count, stride, fixed_size, req_hdrs):
+def _run(verify, pkts, keys, key_index, offsets, buf_sizes, count, stride, fixed_size, req_hdrs, key_table=None):
+    blob, koff, klen, _ = _key_table(keys, key_table)
     L = radius_lib()
-    blob, koff, klen = _key_table(keys)
     fn = L.radius_pkt_verify_batch if verify else L.radius_pkt_sign_batch
     if _is_dev(pkts):
         count, stride, fixed_size, err = _dev_batch(pkts, count, offsets, buf_sizes, stride, fixed_size, None, 4,
@@ -122,7 +112,7 @@ def _run(verify, pkts, keys, key_index, offsets, buf_sizes, count, stride, fixed
                 raise ValueError("req_hdrs holds %d bytes, %d x 20 needed" % (int(req_hdrs.numel()), count))
         err = err.view(torch.int32).reshape(count)
         args = [_ptr(pkts), _ptr(offsets), _ptr(buf_sizes), count, stride, fixed_size, blob.ctypes.data,
-                koff.ctypes.data, klen.ctypes.data, len(klen), _ptr(key_index)]
+                _ptr(koff), klen.ctypes.data, len(klen), _ptr(key_index)]
         with torch.cuda.device(pkts.device):
             stream = torch.cuda.current_stream(pkts.device).cuda_stream
             check(fn(*(args + ([_ptr(req_hdrs)] if verify else []) + [_ptr(err), F_DEVICE, stream])))
@@ -142,25 +132,29 @@ def _run(verify, pkts, keys, key_index, offsets, buf_sizes, count, stride, fixed
             raise ValueError("req_hdrs holds %d bytes, %d x 20 needed" % (req_hdrs.size, count))
     err = err.view(np.int32).reshape(count)
     args = [pkts.ctypes.data, _ptr(offsets), _ptr(buf_sizes), count, stride, fixed_size, blob.ctypes.data,
-            koff.ctypes.data, klen.ctypes.data, len(klen), _ptr(key_index)]
+            _ptr(koff), klen.ctypes.data, len(klen), _ptr(key_index)]
     check(fn(*(args + ([_ptr(req_hdrs)] if verify else []) + [err.ctypes.data, 0, None])))
     return err
 
 
-def sign_packed(pkts, keys, key_index=None, offsets=None, buf_sizes=None, count=None, stride=0, fixed_size=0):
+def sign_packed(pkts, keys, key_index=None, offsets=None, buf_sizes=None, count=None, stride=0, fixed_size=0,
+                key_table=None):
     """radius_pkt_sign(pkt, buf, NULL, key, key_len, 0) of every packed packet,
     in place (radius.h:1487-1532).  pkts: uint8 CUDA tensor or numpy array;
-    keys: the shared secrets (sequence of bytes, host memory); key_index[i]:
+    keys: the shared secrets (sequence of bytes, host memory), or None with
+    key_table=(blob, key_offsets or None, key_lengths), the caller's own key
+    geometry (liblcb_amd.hash._key_table); key_index[i]:
     packet i's secret (default 0), offsets / buf_sizes or stride / fixed_size:
     where packet i's buffer lies.  Returns errors (int32 per packet); a packet
     with a nonzero error is unchanged."""
-    return _run(False, pkts, keys, key_index, offsets, buf_sizes, count, stride, fixed_size, None)
+    return _run(False, pkts, keys, key_index, offsets, buf_sizes, count, stride, fixed_size, None, key_table)
 
 
 def verify_packed(pkts, keys, key_index=None, offsets=None, buf_sizes=None, count=None, stride=0, fixed_size=0,
-                  req_hdrs=None):
+                  req_hdrs=None, key_table=None):
     """radius_pkt_verify(pkt, key, key_len, pkt_req) of every packed packet
     (radius.h:1535-1568); req_hdrs: req_headers(requests) in the batch's kind
-    of memory, or None.  Returns errors; the User-Password of a packet with
-    errors[i] == 0 is decoded in place, nothing else changes."""
-    return _run(True, pkts, keys, key_index, offsets, buf_sizes, count, stride, fixed_size, req_hdrs)
+    of memory, or None; keys / key_table as sign_packed.  Returns errors; the
+    User-Password of a packet with errors[i] == 0 is decoded in place, nothing
+    else changes."""
+    return _run(True, pkts, keys, key_index, offsets, buf_sizes, count, stride, fixed_size, req_hdrs, key_table)

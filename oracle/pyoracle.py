@@ -67,13 +67,29 @@ class _Batch:
         return out
 
     def batch_keyed(self, alg, mode, keys, data, key_index=None, offsets=None, lengths=None, count=None,
-                    stride=0, fixed_len=0):
+                    stride=0, fixed_len=0, key_table=None):
         """Keyed batch (or_batch_keyed / ref_batch_keyed): mode 1 HMAC, 2 H(K || m),
-        3 H(m || K); keys: list of bytes."""
-        blob = np.frombuffer(b"".join(keys) or b"\0", np.uint8)
-        klen = np.array([len(k) for k in keys], np.uint32)
-        koff = np.zeros(len(keys), np.uint64)
-        koff[1:] = np.cumsum(klen[:-1], dtype=np.uint64)
+        3 H(m || K); keys: list of bytes, or None with key_table=(blob,
+        key_offsets or None, key_lengths), passed on as it is (any offsets;
+        None: every key starts at blob[0])."""
+        if key_table is not None:
+            assert keys is None, "keys or key_table, not both"
+            blob, koff, klen = key_table
+            blob = np.ascontiguousarray(np.frombuffer(bytes(blob), np.uint8) if isinstance(
+                blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8)
+            if blob.size == 0:
+                blob = np.zeros(1, np.uint8)
+            klen = np.ascontiguousarray(klen, dtype=np.uint32)
+            if koff is not None:
+                koff = np.ascontiguousarray(koff, dtype=np.uint64)
+                assert koff.size == klen.size
+            nkeys = int(klen.size)
+        else:
+            blob = np.frombuffer(b"".join(keys) or b"\0", np.uint8)
+            klen = np.array([len(k) for k in keys], np.uint32)
+            koff = np.zeros(len(keys), np.uint64)
+            koff[1:] = np.cumsum(klen[:-1], dtype=np.uint64)
+            nkeys = len(keys)
         data = np.ascontiguousarray(data, dtype=np.uint8)
         if data.size == 0:
             data = np.zeros(1, np.uint8)
@@ -86,7 +102,8 @@ class _Batch:
         if count is None:
             count = len(lengths) if lengths is not None else len(offsets)
         out = np.zeros((count, DSIZE[alg]), np.uint8)
-        rc = self.fn_keyed(alg, mode, blob.ctypes.data, koff.ctypes.data, klen.ctypes.data, len(keys),
+        rc = self.fn_keyed(alg, mode, blob.ctypes.data, koff.ctypes.data if koff is not None else None,
+                                     klen.ctypes.data, nkeys,
                                      key_index.ctypes.data if key_index is not None else None, data.ctypes.data,
                                      offsets.ctypes.data if offsets is not None else None,
                                      lengths.ctypes.data if lengths is not None else None, count, stride,

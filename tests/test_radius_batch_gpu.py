@@ -40,10 +40,12 @@ def _find(pkt, t):
     return find_attr(pkt, t)
 
 
-def run(rb, verify, device, packets, keys, kidx, reqs=None, layout="offsets", seed=1, sizes=None):
+def run(rb, verify, device, packets, keys, kidx, reqs=None, layout="offsets", seed=1, sizes=None, key_table=None):
     """Sign or verify `packets` (list of bytes buffers) laid out with random
     0..6-byte gaps (every start phase mod 8) or at stride 4096, canary bytes
-    everywhere else.  -> (errors list, buffers list, blob before, blob after, offsets, buffer sizes)."""
+    everywhere else; the secrets as the list `keys`, or keys None and
+    key_table=(blob, key_offsets or None, key_lengths).
+    -> (errors list, buffers list, blob before, blob after, offsets, buffer sizes)."""
     import torch
     n = len(packets)
     rng = np.random.default_rng(seed)
@@ -62,6 +64,8 @@ def run(rb, verify, device, packets, keys, kidx, reqs=None, layout="offsets", se
     before = blob.copy()
     ki = np.asarray(kidx, np.uint32)
     rh = rb.req_headers(reqs) if reqs is not None else None
+    if key_table is not None:
+        kw["key_table"] = key_table
     if device:
         dev = lambda a, dt=None: torch.as_tensor(a if dt is None else a.astype(dt), device="cuda")  # noqa: E731
         d = dev(blob)

@@ -362,6 +362,63 @@ def test_wrapper_validation_host():
         liblcb_amd.hash_batch_multi([0], 1, d, offsets=offs, lengths=lens, copy_parts=True)
 
 
+def test_wrapper_validation_key_table():
+    """key_table=(blob, key_offsets or None, key_lengths), the caller's own key
+    geometry, is checked like the other host arrays before the C-ABI (which
+    trusts it) is called: it excludes `keys`, the dtypes are the ones the
+    C-ABI reads, as many offsets as lengths, every key inside the blob (no
+    GPU needed).  hash_batch_keyed, sign_packed and verify_packed alike."""
+    import liblcb_amd
+    from liblcb_amd import radius_batch as rb
+    n = 8
+    d = np.zeros(n * 64, np.uint8)
+    offs = np.arange(n, dtype=np.uint64) * 64
+    lens = np.full(n, 64, np.uint32)
+    blob = np.arange(100, dtype=np.uint8)
+    ko, kl = np.array([10, 0, 50], np.uint64), np.array([20, 5, 50], np.uint32)
+    calls = [lambda keys, kt: liblcb_amd.hash_batch_keyed(1, 1, keys, d, offsets=offs, lengths=lens, key_table=kt),
+             lambda keys, kt: rb.sign_packed(d.copy(), keys, offsets=offs, buf_sizes=lens, key_table=kt),
+             lambda keys, kt: rb.verify_packed(d.copy(), keys, offsets=offs, buf_sizes=lens, key_table=kt)]
+    bad = [(ValueError, KEYS, (blob, ko, kl)),                              # both
+           (ValueError, None, None),                                        # neither
+           (TypeError, None, (blob, ko)),                                   # not a triple
+           (TypeError, None, (blob.astype(np.int8), ko, kl)),               # blob dtype
+           (TypeError, None, (blob, ko.astype(np.uint32), kl)),             # offsets read as uint64
+           (TypeError, None, (blob, ko.astype(np.float64), kl)),
+           (TypeError, None, (blob, ko, kl.astype(np.uint64))),             # lengths read as uint32
+           (TypeError, None, (blob, ko, kl.astype(np.uint16))),
+           (TypeError, None, (blob, ko.tolist(), kl)),                      # not arrays
+           (TypeError, None, (blob, ko, kl.tolist())),
+           (TypeError, None, (blob, np.zeros(6, np.uint64)[::2], kl)),      # not contiguous
+           (TypeError, None, (blob, ko, np.zeros(6, np.uint32)[::2])),
+           (TypeError, None, (blob, ko.reshape(3, 1), kl)),
+           (ValueError, None, (blob, ko[:2], kl)),                          # fewer offsets than lengths
+           (ValueError, None, (blob, np.append(ko, np.uint64(0)), kl)),     # more
+           (ValueError, None, (blob, ko[:0], kl[:0])),                      # no key
+           (ValueError, None, (blob, None, kl[:0])),
+           (ValueError, None, (blob, np.array([10, 0, 51], np.uint64), kl)),             # one byte past the blob
+           (ValueError, None, (blob, np.array([10, 100, 50], np.uint64), kl)),
+           (ValueError, None, (blob, np.array([10, 2 ** 64 - 3, 50], np.uint64), kl)),   # offset + length wraps
+           (ValueError, None, (blob, np.array([10, -1, 50], np.int64), kl)),
+           (ValueError, None, (blob, ko, np.array([20, -5, 50], np.int32))),
+           (ValueError, None, (blob, None, np.array([20, 101], np.uint32))),             # NULL offsets: from byte 0
+           (ValueError, None, (b"", None, np.array([1], np.uint32)))]
+    for call in calls:
+        for exc, keys, kt in bad:
+            with pytest.raises(exc):
+                call(keys, kt)
+    # what is allowed reaches the C-ABI: the key table is validated before the library is loaded or called
+    from liblcb_amd.hash import _key_table
+    for kt in ((blob, ko, kl), (bytes(blob), ko.astype(np.int64), kl.astype(np.int32)), (blob, None, kl),
+               (blob, np.array([100, 0], np.uint64), np.array([0, 100], np.uint32)),      # empty key at the end
+               (b"", None, np.zeros(2, np.uint32))):
+        b, o, ln, nk = _key_table(None, kt)
+        assert b.dtype == np.uint8 and b.size >= 1 and nk == len(kt[2]) and (o is None) == (kt[1] is None)
+    b, o, ln, nk = _key_table(KEYS, None)                                   # the keys= path: a running sum
+    assert nk == len(KEYS) and bytes(b) == b"".join(KEYS) and ln.tolist() == [len(k) for k in KEYS]
+    assert o.tolist() == (np.cumsum(ln) - ln).tolist()
+
+
 @pytest.mark.gpu
 def test_keyed_check_epochs_same_stream(gpu, oracle):
     """The device-mode key-index check writes the call's epoch into the
