@@ -142,9 +142,14 @@ def radius_pkt_sign_batch(packets, keys, key_index=None, device=False):
     sequence of bytes (a reply already holds its request's authenticator,
     radius_pkt_reply_init; bytes past Length are kept as they are); keys: the
     shared secrets; key_index[i]: packet i's secret (default 0).  Returns
-    (errors, packets): errors[i] is 0 or the error radius_pkt_sign returns
-    (EINVAL / EOVERFLOW for a User-Password it refuses), and a failed packet
-    is returned unchanged."""
+    (errors, packets): errors[i] is 0 or the error radius_pkt_sign returns:
+    EINVAL / EOVERFLOW for a User-Password it refuses, which is checked first
+    and wins (radius.h:1497-1504), then EBADMSG for a first
+    Message-Authenticator whose length byte is not 18 (radius.h:858 through
+    radius_pkt_attr_msg_authenticator_update, :1519-1523).  A failed packet
+    is returned unchanged (the reference has by then encoded the
+    User-Password of a packet it refuses for its Message-Authenticator:
+    include/lcb_radius_gpu.h, difference 1)."""
     n = len(packets)
     key_index = np.zeros(n, np.uint32) if key_index is None else np.asarray(key_index, np.uint32)
     pkts = [bytearray(p) for p in packets]
@@ -154,6 +159,10 @@ def radius_pkt_sign_batch(packets, keys, key_index=None, device=False):
     # HMAC over the packet with the attribute's 16 data bytes zeroed.
     ma = [(i, find_attr(p, ATTR_MSG_AUTHENTIC)) for i, p in enumerate(pkts) if not err[i]]
     ma = [(i, o) for i, o in ma if o is not None]
+    for i, o in ma:
+        if pkts[i][o + 1] != 18:
+            err[i] = errno.EBADMSG
+    ma = [(i, o) for i, o in ma if not err[i]]
     msgs = []
     for i, o in ma:
         pkts[i][o + 2:o + 18] = bytes(16)

@@ -175,6 +175,27 @@ ref_rad_verify(const uint8_t *pkt_in, size_t len, const uint8_t *key, size_t key
 	return (error);
 }
 
+/* radius_pkt_verify (radius.h:1535) alone, WITHOUT radius_pkt_chk's semantic
+ * filter, of a copy of `pkt` in a zero-filled RADIUS_PKT_MAX_SIZE buffer;
+ * `out` receives the packet after verification.  Only for packets that pass
+ * the structural guard of include/lcb_radius_gpu.h (the caller's own walk,
+ * tests/golden/make_golden_radius_matrix.py), so the find loop stays inside
+ * [0, Length). */
+int
+ref_rad_verify_raw(const uint8_t *pkt_in, size_t len, const uint8_t *key, size_t key_len,
+    const uint8_t *req, uint8_t *out) {
+	uint8_t buf[RADIUS_PKT_MAX_SIZE];
+	int error;
+
+	if (len > sizeof(buf))
+		return (EINVAL);
+	memset(buf, 0, sizeof(buf));
+	memcpy(buf, pkt_in, len);
+	error = radius_pkt_verify((rad_pkt_hdr_p)buf, (uint8_t*)key, key_len, (rad_pkt_hdr_p)req);
+	memcpy(out, buf, len);
+	return (error);
+}
+
 /* radius_pkt_authenticator_calc (radius.h:1315) on a copy of `pkt`. */
 int
 ref_rad_authenticator_calc(const uint8_t *pkt_in, size_t len, const uint8_t *key, size_t key_len,

@@ -40,17 +40,18 @@ def _find(pkt, t):
     return find_attr(pkt, t)
 
 
-def run(rb, verify, device, packets, keys, kidx, reqs=None, layout="offsets", seed=1, sizes=None, key_table=None):
+def run(rb, verify, device, packets, keys, kidx, reqs=None, layout="offsets", seed=1, sizes=None, key_table=None,
+        gap_max=7):
     """Sign or verify `packets` (list of bytes buffers) laid out with random
-    0..6-byte gaps (every start phase mod 8) or at stride 4096, canary bytes
-    everywhere else; the secrets as the list `keys`, or keys None and
+    0..gap_max-1-byte gaps (0..6: every start phase mod 8) or at stride 4096,
+    canary bytes everywhere else; the secrets as the list `keys`, or keys None and
     key_table=(blob, key_offsets or None, key_lengths).
     -> (errors list, buffers list, blob before, blob after, offsets, buffer sizes)."""
     import torch
     n = len(packets)
     rng = np.random.default_rng(seed)
     if layout == "offsets":
-        blob, offs, bsz = rb.pack(packets, gaps=rng.integers(0, 7, n) + (np.arange(n) == 0) * 3, fill=CANARY)
+        blob, offs, bsz = rb.pack(packets, gaps=rng.integers(0, gap_max, n) + (np.arange(n) == 0) * 3, fill=CANARY)
         blob = np.concatenate([blob, np.full(16, CANARY, np.uint8)])
         kw = dict(offsets=offs, buf_sizes=bsz)
     else:

@@ -5,7 +5,11 @@ in a heap block of exactly its buffer size, so a read outside the buffer ends
 the program with a report; the records it prints are compared with a small
 Python model: a find_attr-style walk plus the guard rules of
 include/lcb_radius_gpu.h, and the step plan from liblcb_amd.radius's code
-tables.  Nothing is loaded into Python and nothing is preloaded."""
+tables.  The packets of tests/golden/radius_matrix.json (every code, layout
+and request, the 4096-byte ones and a list of 2038 two-byte attributes) go
+through the same program, and its verdicts for them are also held against the
+REFERENCE's result codes in that fixture, with no Python model in between.
+Nothing is loaded into Python and nothing is preloaded."""
 import errno
 import json
 import os
@@ -81,8 +85,31 @@ def model(pkt, key_index, nkeys, req_code):
     return rec + [sign, e1, e2, e3, p_ma, p_au, p_pw, ma_mode if p_ma else None, au_mode if p_au else None]
 
 
-def records():
-    """(packet buffer, key_index, nkeys, req_code) for every case."""
+@pytest.fixture(scope="module")
+def matrix(oracle):
+    """The packets of radius_matrix.json as verify sees them (signed; as built
+    where sign refuses), checked against the fixture's hashes, each with its
+    request's code: (fixture cases, records)."""
+    from tests.test_radius_matrix import Matrix
+    mx = Matrix(oracle, verify=False)
+    return mx.cases, [(b, c["key"], len(mx.secrets), c["request"]) for b, c in zip(mx.inputs("verify"), mx.cases)]
+
+
+def walk(exe, recs):
+    """The program's 16 numbers for every record, under the sanitizers."""
+    blob = b"".join(struct.pack("<IIII", len(b), k, n, r) + b for b, k, n, r in recs)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    res = subprocess.run([exe], input=blob, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    assert res.returncode == 0, res.stderr.decode()[-2000:]
+    lines = res.stdout.decode().splitlines()
+    assert len(lines) == len(recs)
+    return [[int(x) for x in line.split()] for line in lines]
+
+
+def records(matrix=()):
+    """(packet buffer, key_index, nkeys, req_code) for every case; `matrix`:
+    the records of radius_matrix.json, appended with the longest attribute list
+    a packet can hold (2038 two-byte attributes) under three codes."""
     P = json.load(open(os.path.join(G, "radius.json")))["packets"]
     base = [(bytes.fromhex(p["signed"]), p["key"], 5, bytes.fromhex(p["request"])[0] if p["kind"] == "reply" else 0)
             for p in P]
@@ -118,21 +145,19 @@ def records():
         at = spots[int(rng.integers(0, len(spots)))] if m % 3 else 3
         b[at] = int(rng.integers(0, 256)) if m % 5 else (b[at] + int(rng.integers(-2, 3))) & 0xFF
         out.append((bytes(b), k, n, r))
+    if matrix:
+        from tests.radius_matrix_util import full_two_byte_only
+        out += list(matrix)
+        out += [(full_two_byte_only(code), 1, 4, r) for code, r in ((4, 0), (2, 1), (99, 12))]
     return out
 
 
-def test_parse_records_match_model_under_sanitizers(exe):
-    recs = records()
-    assert len(recs) > 5000
-    blob = b"".join(struct.pack("<IIII", len(b), k, n, r) + b for b, k, n, r in recs)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    res = subprocess.run([exe], input=blob, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
-    assert res.returncode == 0, res.stderr.decode()[-2000:]
-    lines = res.stdout.decode().splitlines()
-    assert len(lines) == len(recs)
+def test_parse_records_match_model_under_sanitizers(exe, matrix):
+    recs = records(matrix[1])
+    assert len(recs) > 5000 + len(matrix[1])
+    assert sum(1 for b, _, _, _ in recs if len(b) == 4096) >= 280 + 3
     seen = set()
-    for (b, k, n, r), line in zip(recs, lines):
-        got = [int(x) for x in line.split()]
+    for (b, k, n, r), got in zip(recs, walk(exe, recs)):
         want = model(b, k, n, r)
         assert len(got) == 16
         for g, w in zip(got, want):
@@ -143,3 +168,26 @@ def test_parse_records_match_model_under_sanitizers(exe):
     assert {0, errno.EINVAL, errno.EOVERFLOW} <= {s[1] for s in seen}
     assert {0, E, errno.EINVAL} <= {s[2] for s in seen}
     assert {0, errno.EINVAL} <= {s[3] for s in seen} and {0, errno.EINVAL} <= {s[4] for s in seen}
+
+
+def test_matrix_verdicts_consistent_with_reference(exe, matrix):
+    """No Python model: what the compiled walk decides without a hash must
+    agree with what the reference returned for the same packet and request
+    (radius_matrix.json; verify as built, untampered)."""
+    cases, recs = matrix
+    n_e1 = n_inval = n_ok = 0
+    for c, rec, got in zip(cases, recs, walk(exe, recs)):
+        err, sign, e1, e2, e3 = got[0], got[7], got[8], got[9], got[10]
+        what = (c, got)
+        assert err == 0, what
+        assert sign == c["sign"], what
+        if e1:
+            assert c["verify"] == e1, what
+            n_e1 += 1
+        elif c["verify"] == errno.EINVAL:
+            assert errno.EINVAL in (e2, e3), what
+            n_inval += 1
+        elif c["verify"] == 0:
+            assert (e1, e2, e3) == (0, 0, 0), what
+            n_ok += 1
+    assert n_e1 > 100 and n_inval > 100 and 3 * n_ok >= len(cases)
