@@ -1,0 +1,29 @@
+// ecdsa_internal.hpp — types shared by the kernel TU and the C-ABI TU of
+// liblcb_ecdsa_gpu.so (include/lcb_ecdsa_gpu.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ecdsa_math.hpp"
+
+namespace lcbec {
+
+constexpr int kLimbs = 8;  // 256-bit curves; a 384-bit build is kLimbs = 12
+constexpr int kNumBytes = 4 * kLimbs;
+
+// Device-side description of one verification batch.
+struct EcArgs {
+    const uint8_t* hashes = nullptr;    // count x hash_size
+    const uint8_t* sigs = nullptr;      // count x 2 kNumBytes: r || s
+    const uint8_t* keys = nullptr;      // nkeys x 2 kNumBytes: x || y
+    const uint32_t* key_idx = nullptr;  // nullptr: key i for item i
+    int32_t* status = nullptr;          // count
+    uint64_t count = 0, nkeys = 0;
+    uint32_t hash_size = 0;
+    uint32_t le = 0;
+};
+
+// The per-curve constant block travels as a kernel argument (scalar loads).
+void launch_ecdsa_verify(const EcArgs& a, const Curve<kLimbs>& c, hipStream_t s);
+
+}  // namespace lcbec
