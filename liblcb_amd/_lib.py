@@ -160,6 +160,38 @@ def lib():
     return _lib
 
 
+ECDSA_DH_LIB_PATH = os.path.join(HERE, "liblcb_ecdsa_dh_gpu.so")
+_DH = [ctypes.c_int, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_u32, c_vp]
+# every symbol include/lcb_ecdsa_dh_gpu.h declares
+ECDSA_DH_SIGNATURES = [
+    ("lcb_ecdsa_dh_batch", ctypes.c_int, [ctypes.c_int, ctypes.c_int] + _DH),
+    ("ecdsa_dh_be_batch", ctypes.c_int, [ctypes.c_int] + _DH),
+    ("ecdsa_dh_le_batch", ctypes.c_int, [ctypes.c_int] + _DH),
+]
+_dhlib = None
+
+
+def ecdsa_dh_lib():
+    """The loaded liblcb_ecdsa_dh_gpu.so (after liblcb_hash_gpu.so, which it
+    links against); raises LcbHashError if it has not been built."""
+    global _dhlib
+    if _dhlib is None:
+        lib()
+        if not os.path.exists(ECDSA_DH_LIB_PATH):
+            raise LcbHashError(2, "%s is missing: build it with `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C liblcb_amd`)" % ECDSA_DH_LIB_PATH)
+        try:
+            L = ctypes.CDLL(ECDSA_DH_LIB_PATH)
+        except OSError as e:
+            raise LcbHashError(2, "%s does not load: %s" % (ECDSA_DH_LIB_PATH, e))
+        for name, res, args in ECDSA_DH_SIGNATURES:
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _dhlib = L
+    return _dhlib
+
+
 def check(rc):
     if rc != 0:
         msg = lib().lcb_hash_strerror(rc).decode()
