@@ -160,6 +160,25 @@ def lib():
     return _lib
 
 
+def load_satellite(path, signatures):
+    """The library at `path`, one built beside liblcb_hash_gpu.so and linked
+    against it, loaded after it with `signatures` bound; raises LcbHashError
+    if it has not been built."""
+    lib()
+    if not os.path.exists(path):
+        raise LcbHashError(2, "%s is missing: build it with `python -c 'import __graft_entry__ as g; "
+                           "g.build()'` (or `make -C liblcb_amd`)" % path)
+    try:
+        L = ctypes.CDLL(path)
+    except OSError as e:
+        raise LcbHashError(2, "%s does not load: %s" % (path, e))
+    for name, res, args in signatures:
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    return L
+
+
 ECDSA_DH_LIB_PATH = os.path.join(HERE, "liblcb_ecdsa_dh_gpu.so")
 _DH = [ctypes.c_int, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_u32, c_vp]
 # every symbol include/lcb_ecdsa_dh_gpu.h declares
@@ -176,19 +195,7 @@ def ecdsa_dh_lib():
     links against); raises LcbHashError if it has not been built."""
     global _dhlib
     if _dhlib is None:
-        lib()
-        if not os.path.exists(ECDSA_DH_LIB_PATH):
-            raise LcbHashError(2, "%s is missing: build it with `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C liblcb_amd`)" % ECDSA_DH_LIB_PATH)
-        try:
-            L = ctypes.CDLL(ECDSA_DH_LIB_PATH)
-        except OSError as e:
-            raise LcbHashError(2, "%s does not load: %s" % (ECDSA_DH_LIB_PATH, e))
-        for name, res, args in ECDSA_DH_SIGNATURES:
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _dhlib = L
+        _dhlib = load_satellite(ECDSA_DH_LIB_PATH, ECDSA_DH_SIGNATURES)
     return _dhlib
 
 

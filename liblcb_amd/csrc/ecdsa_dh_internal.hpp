@@ -8,9 +8,6 @@
 
 namespace lcbec {
 
-constexpr int kLimbs = 8;  // 256-bit curves
-constexpr int kNumBytes = 4 * kLimbs;
-
 // Device-side description of one key agreement batch.
 struct DhArgs {
     const uint8_t* pub = nullptr;        // npub x 2 kNumBytes: x || y

@@ -20,7 +20,6 @@
 #include <stdint.h>
 
 #include "ecdsa_math.hpp"
-#include "ecdsa_sign_math.hpp"  // store_num, jac_to_affine
 
 namespace lcbec {
 

@@ -8,9 +8,6 @@
 
 namespace lcbec {
 
-constexpr int kLimbs = 8;  // 256-bit curves; a 384-bit build is kLimbs = 12
-constexpr int kNumBytes = 4 * kLimbs;
-
 // Device-side description of one verification batch.
 struct EcArgs {
     const uint8_t* hashes = nullptr;    // count x hash_size

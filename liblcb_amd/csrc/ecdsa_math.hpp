@@ -33,6 +33,8 @@ namespace lcbec {
 constexpr int kEinval = 22;  // EINVAL of the reference's platforms
 constexpr int kBadPoint = -1;
 constexpr int kBadSign = -2;
+constexpr int kLimbs = 8;  // 256-bit curves; a 384-bit build is kLimbs = 12
+constexpr int kNumBytes = 4 * kLimbs;
 enum { kAlgoEcdsa = 0, kAlgoGost = 1 };
 enum { kAGeneral = 0, kAZero = 1, kAMinus3 = 2 };  // Curve::a_kind
 
@@ -334,6 +336,15 @@ EC_HD EC_INLINE Jac<L> jac_add_affine(const Jac<L>& P, const Num<L>& x2, const N
     return R;
 }
 
+// Affine x (and y where wanted) of R, Z != 0, as plain numbers below p.
+template <int L>
+EC_HD EC_INLINE void jac_to_affine(const Jac<L>& R, const Mod<L>& F, Num<L>& x, Num<L>* y) {
+    const Num<L> zi = mont_inv(R.Z, F);
+    const Num<L> zi2 = mont_mul(zi, zi, F);
+    x = from_mont(mont_mul(R.X, zi2, F), F);
+    if (y) *y = from_mont(mont_mul(R.Y, mont_mul(zi2, zi, F), F), F);
+}
+
 // ------------------------------------------------------------------- import
 // The number in p[0 .. nbytes), nbytes <= 4 L, big-endian or little-endian.
 // No byte outside p[0 .. nbytes) is read.
@@ -351,6 +362,19 @@ EC_HD EC_INLINE Num<L> load_num(const uint8_t* p, uint32_t nbytes, bool le) {
         r.w[j] = v;
     }
     return r;
+}
+
+// The number a as 4 L bytes at p, big-endian or little-endian.
+template <int L>
+EC_HD EC_INLINE void store_num(uint8_t* p, const Num<L>& a, bool le) {
+    EC_UNROLL
+    for (int j = 0; j < L; ++j) {
+        EC_UNROLL
+        for (int k = 0; k < 4; ++k) {
+            const int q = 4 * j + k;  // byte of significance 256^q
+            p[le ? q : 4 * L - 1 - q] = (uint8_t)(a.w[j] >> (8 * k));
+        }
+    }
 }
 
 // ------------------------------------------------------------------- verify

@@ -8,8 +8,6 @@
 
 namespace lcbec {
 
-constexpr int kLimbs = 8;  // 256-bit curves
-constexpr int kNumBytes = 4 * kLimbs;
 typedef BaseTable<kLimbs> Table;
 
 // Device-side description of one signing batch.

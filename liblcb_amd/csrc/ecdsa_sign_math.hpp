@@ -61,19 +61,6 @@ EC_HD EC_INLINE Num<L> bn_mod_reduce(const Num<L>& v, const Num<L>& m) {
     return select(geq(v, m), t, v);
 }
 
-// The number a as 4 L bytes at p, big-endian or little-endian.
-template <int L>
-EC_HD EC_INLINE void store_num(uint8_t* p, const Num<L>& a, bool le) {
-    EC_UNROLL
-    for (int j = 0; j < L; ++j) {
-        EC_UNROLL
-        for (int k = 0; k < 4; ++k) {
-            const int q = 4 * j + k;  // byte of significance 256^q
-            p[le ? q : 4 * L - 1 - q] = (uint8_t)(a.w[j] >> (8 * k));
-        }
-    }
-}
-
 // ------------------------------------------------------ fixed-base multiple
 // k G for k < 16^(8 L); the point at infinity (Z = 0) for k = 0.
 template <int L>
@@ -103,15 +90,6 @@ EC_HD EC_INLINE Jac<L> base_mult(const Curve<L>& C, const BaseTable<L>* T, Num<L
         R.Z = select(take, S.Z, R.Z);
     }
     return R;
-}
-
-// Affine x (and y where wanted) of R, Z != 0, as plain numbers below p.
-template <int L>
-EC_HD EC_INLINE void jac_to_affine(const Jac<L>& R, const Mod<L>& F, Num<L>& x, Num<L>* y) {
-    const Num<L> zi = mont_inv(R.Z, F);
-    const Num<L> zi2 = mont_mul(zi, zi, F);
-    x = from_mont(mont_mul(R.X, zi2, F), F);
-    if (y) *y = from_mont(mont_mul(R.Y, mont_mul(zi2, zi, F), F), F);
 }
 
 // --------------------------------------------------------------------- sign

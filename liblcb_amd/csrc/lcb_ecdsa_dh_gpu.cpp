@@ -1,16 +1,17 @@
 // lcb_ecdsa_dh_gpu.cpp — exported C-ABI of batched ECDH key agreement
 // (include/lcb_ecdsa_dh_gpu.h), built into liblcb_ecdsa_dh_gpu.so and linked
 // against liblcb_hash_gpu.so for the shared runtime pieces (ensure_init,
-// map_err).  The curve table is ecdsa_curves.hpp, included here; neither the
-// verification nor the signing library is linked.
+// map_err).  The curve table is ecdsa_curves.hpp, parsed here by
+// ecdsa_host.hpp; neither the verification nor the signing library is linked.
 //
 // Device mode enqueues one kernel on the caller's stream and never
 // synchronises.  Host mode stages chunk by chunk through page-locked memory on
 // a private stream: copy -> H2D -> kernel -> D2H -> copy, one chunk in flight;
 // a key table that goes with an index array is staged whole, once.  After the
 // last chunk every staging buffer, page-locked and on the device, is
-// overwritten with zeros: they held private keys and shared secrets.  Nothing
-// falls back to the CPU.
+// overwritten with zeros: they held private keys and shared secrets (the
+// staging context and its wipe() are host_stage.hpp's).  Nothing falls back
+// to the CPU.
 #include <errno.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -22,8 +23,9 @@
 
 #include "../../include/lcb_ecdsa_dh_gpu.h"
 #include "../../include/lcb_hash_gpu.h"
-#include "ecdsa_curves.hpp"
+#include "ecdsa_host.hpp"
 #include "ecdsa_dh_internal.hpp"
+#include "host_stage.hpp"
 #include "lcb_internal.hpp"
 
 using namespace lcbgpu;
@@ -31,93 +33,9 @@ using namespace lcbec;
 
 namespace {
 
-#define EC_TRY(expr)                              \
-    do {                                          \
-        hipError_t _e = (expr);                   \
-        if (_e != hipSuccess) return map_err(_e); \
-    } while (0)
-
-static_assert(kEinval == EINVAL, "the kernel's EINVAL is the host's");
-
-// The curve table parsed and its Montgomery constants derived, once.
-struct CurveTable {
-    Curve<kLimbs> c[kCurveCount];
-    bool ok[kCurveCount];
-    CurveTable() {
-        for (int id = 0; id < kCurveCount; ++id) {
-            uint8_t raw[6 * kNumBytes];
-            for (int k = 0; k < 6; ++k)
-                for (int i = 0; i < kNumBytes; ++i) {
-                    auto nib = [](char ch) { return (uint8_t)(ch <= '9' ? ch - '0' : ch - 'a' + 10); };
-                    const char* h = kCurves[id].num[k] + 2 * i;
-                    raw[kNumBytes * k + i] = (uint8_t)(nib(h[0]) << 4 | nib(h[1]));
-                }
-            ok[id] = curve_setup(c[id], raw, kCurves[id].algo);
-        }
-    }
-};
-
-const CurveTable& table() {
-    static const CurveTable t;
-    return t;
-}
-
-bool known(int id) { return id >= 0 && id < kCurveCount && table().ok[id]; }
-
 // ------------------------------------------------------------ host mode
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-struct DhStage {
-    int device = -1;
-    size_t cap = 0, kcap = 0;  // bytes per chunk / bytes of the key tables
-    hipStream_t st = nullptr;
-    uint8_t *h = nullptr, *d = nullptr;    // one chunk: inputs | outputs | status
-    uint8_t *hk = nullptr, *dk = nullptr;  // the whole key tables of an indexed batch
-
-    void release() {
-        if (h) (void)hipHostFree(h);
-        if (hk) (void)hipHostFree(hk);
-        if (d) (void)hipFree(d);
-        if (dk) (void)hipFree(dk);
-        if (st) (void)hipStreamDestroy(st);
-        h = d = hk = dk = nullptr;
-        st = nullptr;
-        cap = kcap = 0;
-        device = -1;
-    }
-    ~DhStage() { release(); }
-
-    int ensure(int dev, size_t bytes, size_t key_bytes) {
-        if (device == dev && cap >= bytes && kcap >= key_bytes) return 0;
-        const size_t nb = std::max(bytes, cap), nk = std::max(key_bytes, kcap);
-        release();
-        device = dev;
-        EC_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        EC_TRY(hipHostMalloc(reinterpret_cast<void**>(&h), nb, hipHostMallocDefault));
-        EC_TRY(hipMalloc(reinterpret_cast<void**>(&d), nb));
-        if (nk) {
-            EC_TRY(hipHostMalloc(reinterpret_cast<void**>(&hk), nk, hipHostMallocDefault));
-            EC_TRY(hipMalloc(reinterpret_cast<void**>(&dk), nk));
-        }
-        cap = nb;
-        kcap = nk;
-        return 0;
-    }
-
-    // Zeros over everything a call staged (`bytes` of the chunk buffers,
-    // `key_bytes` of the key tables), on the host and on the device; waits.
-    int wipe(size_t bytes, size_t key_bytes) {
-        hipError_t e = hipSuccess, e2;
-        if (h) memset(h, 0, std::min(bytes, cap));
-        if (hk) memset(hk, 0, std::min(key_bytes, kcap));
-        if (d && st && (e2 = hipMemsetAsync(d, 0, std::min(bytes, cap), st)) != hipSuccess) e = e2;
-        if (dk && st && key_bytes && (e2 = hipMemsetAsync(dk, 0, std::min(key_bytes, kcap), st)) != hipSuccess) e = e2;
-        if (st && (e2 = hipStreamSynchronize(st)) != hipSuccess) e = e2;
-        return e == hipSuccess ? 0 : map_err(e);
-    }
-};
-
-thread_local DhStage g_stage;
+// h / d: one chunk.  h2 / d2: the whole key tables of an indexed batch.
+thread_local HostStage g_stage;
 constexpr size_t kChunkItems = 1u << 18;
 
 // One chunk: pub | priv | pub_idx | priv_idx | shared | status.  A part whose
@@ -126,13 +44,13 @@ struct DhLayout {
     size_t chunk, o_priv, o_pidx, o_didx, o_out, o_st, bytes, k_priv, key_bytes;
 };
 
-int dh_chunks(DhStage& S, const DhLayout& y, const Curve<kLimbs>& c, int le, const uint8_t* pub, size_t npub,
+int dh_chunks(HostStage& S, const DhLayout& y, const Curve<kLimbs>& c, int le, const uint8_t* pub, size_t npub,
               const uint32_t* pub_idx, const uint8_t* priv, size_t npriv, const uint32_t* priv_idx, size_t count,
               uint8_t* shared, int32_t* status) {
     if (y.key_bytes) {
-        if (pub_idx) memcpy(S.hk, pub, npub * 2 * kNumBytes);
-        if (priv_idx) memcpy(S.hk + y.k_priv, priv, npriv * kNumBytes);
-        EC_TRY(hipMemcpyAsync(S.dk, S.hk, y.key_bytes, hipMemcpyHostToDevice, S.st));
+        if (pub_idx) memcpy(S.h2, pub, npub * 2 * kNumBytes);
+        if (priv_idx) memcpy(S.h2 + y.k_priv, priv, npriv * kNumBytes);
+        LCB_HOST_TRY(hipMemcpyAsync(S.d2, S.h2, y.key_bytes, hipMemcpyHostToDevice, S.st));
     }
     for (size_t i = 0; i < count; i += y.chunk) {
         const size_t n = std::min(y.chunk, count - i);
@@ -144,11 +62,11 @@ int dh_chunks(DhStage& S, const DhLayout& y, const Curve<kLimbs>& c, int le, con
             memcpy(S.h + y.o_didx, priv_idx + i, n * 4);
         else
             memcpy(S.h + y.o_priv, priv + i * kNumBytes, n * kNumBytes);
-        EC_TRY(hipMemcpyAsync(S.d, S.h, y.o_out, hipMemcpyHostToDevice, S.st));
+        LCB_HOST_TRY(hipMemcpyAsync(S.d, S.h, y.o_out, hipMemcpyHostToDevice, S.st));
         DhArgs a;
-        a.pub = pub_idx ? S.dk : S.d;
+        a.pub = pub_idx ? S.d2 : S.d;
         a.pub_idx = pub_idx ? reinterpret_cast<const uint32_t*>(S.d + y.o_pidx) : nullptr;
-        a.priv = priv_idx ? S.dk + y.k_priv : S.d + y.o_priv;
+        a.priv = priv_idx ? S.d2 + y.k_priv : S.d + y.o_priv;
         a.priv_idx = priv_idx ? reinterpret_cast<const uint32_t*>(S.d + y.o_didx) : nullptr;
         a.shared = S.d + y.o_out;
         a.status = reinterpret_cast<int32_t*>(S.d + y.o_st);
@@ -157,9 +75,10 @@ int dh_chunks(DhStage& S, const DhLayout& y, const Curve<kLimbs>& c, int le, con
         a.npriv = priv_idx ? npriv : n;
         a.le = le ? 1u : 0u;
         launch_ecdsa_dh(a, c, S.st);
-        EC_TRY(hipGetLastError());
-        EC_TRY(hipMemcpyAsync(S.h + y.o_out, S.d + y.o_out, y.o_st - y.o_out + n * 4, hipMemcpyDeviceToHost, S.st));
-        EC_TRY(hipStreamSynchronize(S.st));
+        LCB_HOST_TRY(hipGetLastError());
+        LCB_HOST_TRY(
+            hipMemcpyAsync(S.h + y.o_out, S.d + y.o_out, y.o_st - y.o_out + n * 4, hipMemcpyDeviceToHost, S.st));
+        LCB_HOST_TRY(hipStreamSynchronize(S.st));
         memcpy(shared + i * kNumBytes, S.h + y.o_out, n * kNumBytes);
         memcpy(status + i, S.h + y.o_st, n * 4);
     }
@@ -170,7 +89,7 @@ int dh_host(const Curve<kLimbs>& c, int le, const uint8_t* pub, size_t npub, con
             const uint8_t* priv, size_t npriv, const uint32_t* priv_idx, size_t count, uint8_t* shared,
             int32_t* status) {
     int dev = 0;
-    EC_TRY(hipGetDevice(&dev));
+    LCB_HOST_TRY(hipGetDevice(&dev));
     DhLayout y;
     y.chunk = std::min(count, kChunkItems);
     y.o_priv = pub_idx ? 0 : y.chunk * 2 * kNumBytes;

@@ -7,8 +7,9 @@
 // synchronises; the per-curve constant block travels as a kernel argument.
 // Host mode stages chunk by chunk through page-locked memory on a private
 // stream: copy -> H2D -> kernel -> D2H -> copy.  It is NOT pipelined (one
-// chunk in flight; the kernel dwarfs the copies).  Nothing falls back to the
-// CPU.
+// chunk in flight; the kernel dwarfs the copies).  The staging context is
+// host_stage.hpp's, the parsed curve table ecdsa_host.hpp's.  It stages only
+// public data and wipes nothing.  Nothing falls back to the CPU.
 #include <errno.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -20,8 +21,9 @@
 
 #include "../../include/lcb_ecdsa_gpu.h"
 #include "../../include/lcb_hash_gpu.h"
-#include "ecdsa_curves.hpp"
+#include "ecdsa_host.hpp"
 #include "ecdsa_internal.hpp"
+#include "host_stage.hpp"
 #include "lcb_internal.hpp"
 
 using namespace lcbgpu;
@@ -29,96 +31,25 @@ using namespace lcbec;
 
 namespace {
 
-#define EC_TRY(expr)                              \
-    do {                                          \
-        hipError_t _e = (expr);                   \
-        if (_e != hipSuccess) return map_err(_e); \
-    } while (0)
-
-static_assert(kEinval == EINVAL, "the kernel's EINVAL is the host's");
-
-// The curve table parsed and its Montgomery constants derived, once.
-struct CurveTable {
-    uint8_t raw[kCurveCount][6 * kNumBytes];
-    Curve<kLimbs> c[kCurveCount];
-    bool ok[kCurveCount];
-    CurveTable() {
-        for (int id = 0; id < kCurveCount; ++id) {
-            for (int k = 0; k < 6; ++k)
-                for (int i = 0; i < kNumBytes; ++i) {
-                    auto nib = [](char ch) { return (uint8_t)(ch <= '9' ? ch - '0' : ch - 'a' + 10); };
-                    const char* h = kCurves[id].num[k] + 2 * i;
-                    raw[id][kNumBytes * k + i] = (uint8_t)(nib(h[0]) << 4 | nib(h[1]));
-                }
-            ok[id] = curve_setup(c[id], raw[id], kCurves[id].algo);
-        }
-    }
-};
-
-const CurveTable& table() {
-    static const CurveTable t;
-    return t;
-}
-
-bool known(int id) { return id >= 0 && id < kCurveCount && table().ok[id]; }
-
 // ------------------------------------------------------------ host mode
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-struct EcStage {
-    int device = -1;
-    size_t cap = 0, kcap = 0;  // bytes per chunk / bytes of the key table
-    hipStream_t st = nullptr;
-    uint8_t *h = nullptr, *d = nullptr;    // one chunk: hashes | sigs | keys | key_idx | status
-    uint8_t *hk = nullptr, *dk = nullptr;  // the whole key table of a key_idx batch
-
-    void release() {
-        if (h) (void)hipHostFree(h);
-        if (hk) (void)hipHostFree(hk);
-        if (d) (void)hipFree(d);
-        if (dk) (void)hipFree(dk);
-        if (st) (void)hipStreamDestroy(st);
-        h = d = hk = dk = nullptr;
-        st = nullptr;
-        cap = kcap = 0;
-        device = -1;
-    }
-    ~EcStage() { release(); }
-
-    int ensure(int dev, size_t bytes, size_t key_bytes) {
-        if (device == dev && cap >= bytes && kcap >= key_bytes) return 0;
-        const size_t nb = std::max(bytes, cap), nk = std::max(key_bytes, kcap);
-        release();
-        device = dev;
-        EC_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        EC_TRY(hipHostMalloc(reinterpret_cast<void**>(&h), nb, hipHostMallocDefault));
-        EC_TRY(hipMalloc(reinterpret_cast<void**>(&d), nb));
-        if (nk) {
-            EC_TRY(hipHostMalloc(reinterpret_cast<void**>(&hk), nk, hipHostMallocDefault));
-            EC_TRY(hipMalloc(reinterpret_cast<void**>(&dk), nk));
-        }
-        cap = nb;
-        kcap = nk;
-        return 0;
-    }
-};
-
-thread_local EcStage g_stage;
+// h / d: one chunk, hashes | sigs | keys | key_idx | status.  h2 / d2: the whole
+// key table of a key_idx batch.
+thread_local HostStage g_stage;
 constexpr size_t kChunkItems = 1u << 18;
 
 int verify_host(const Curve<kLimbs>& c, int le, const uint8_t* hashes, size_t hash_size, const uint8_t* sigs,
                 const uint8_t* keys, size_t nkeys, const uint32_t* key_idx, size_t count, int32_t* status) {
     int dev = 0;
-    EC_TRY(hipGetDevice(&dev));
+    LCB_HOST_TRY(hipGetDevice(&dev));
     const size_t chunk = std::min(count, kChunkItems);
     const size_t o_sig = up16(chunk * hash_size), o_key = o_sig + chunk * 2 * kNumBytes;
     const size_t o_idx = o_key + (key_idx ? 0 : chunk * 2 * kNumBytes), o_st = o_idx + up16(chunk * 4);
     const size_t key_bytes = key_idx ? nkeys * 2 * kNumBytes : 0;
     if (int rc = g_stage.ensure(dev, o_st + chunk * 4, key_bytes)) return rc;
-    EcStage& S = g_stage;
+    HostStage& S = g_stage;
     if (key_bytes) {
-        memcpy(S.hk, keys, key_bytes);
-        EC_TRY(hipMemcpyAsync(S.dk, S.hk, key_bytes, hipMemcpyHostToDevice, S.st));
+        memcpy(S.h2, keys, key_bytes);
+        LCB_HOST_TRY(hipMemcpyAsync(S.d2, S.h2, key_bytes, hipMemcpyHostToDevice, S.st));
     }
     for (size_t i = 0; i < count; i += chunk) {
         const size_t n = std::min(chunk, count - i);
@@ -128,11 +59,11 @@ int verify_host(const Curve<kLimbs>& c, int le, const uint8_t* hashes, size_t ha
             memcpy(S.h + o_idx, key_idx + i, n * 4);
         else
             memcpy(S.h + o_key, keys + i * 2 * kNumBytes, n * 2 * kNumBytes);
-        EC_TRY(hipMemcpyAsync(S.d, S.h, o_st, hipMemcpyHostToDevice, S.st));
+        LCB_HOST_TRY(hipMemcpyAsync(S.d, S.h, o_st, hipMemcpyHostToDevice, S.st));
         EcArgs a;
         a.hashes = S.d;
         a.sigs = S.d + o_sig;
-        a.keys = key_idx ? S.dk : S.d + o_key;
+        a.keys = key_idx ? S.d2 : S.d + o_key;
         a.key_idx = key_idx ? reinterpret_cast<const uint32_t*>(S.d + o_idx) : nullptr;
         a.status = reinterpret_cast<int32_t*>(S.d + o_st);
         a.count = n;
@@ -140,9 +71,9 @@ int verify_host(const Curve<kLimbs>& c, int le, const uint8_t* hashes, size_t ha
         a.hash_size = (uint32_t)hash_size;
         a.le = le ? 1u : 0u;
         launch_ecdsa_verify(a, c, S.st);
-        EC_TRY(hipGetLastError());
-        EC_TRY(hipMemcpyAsync(S.h + o_st, S.d + o_st, n * 4, hipMemcpyDeviceToHost, S.st));
-        EC_TRY(hipStreamSynchronize(S.st));
+        LCB_HOST_TRY(hipGetLastError());
+        LCB_HOST_TRY(hipMemcpyAsync(S.h + o_st, S.d + o_st, n * 4, hipMemcpyDeviceToHost, S.st));
+        LCB_HOST_TRY(hipStreamSynchronize(S.st));
         memcpy(status + i, S.h + o_st, n * 4);
     }
     return 0;

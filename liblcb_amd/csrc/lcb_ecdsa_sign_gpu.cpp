@@ -2,8 +2,8 @@
 // signing, key generation and public keys from private keys
 // (include/lcb_ecdsa_sign_gpu.h), built into liblcb_ecdsa_sign_gpu.so and
 // linked against liblcb_hash_gpu.so for the shared runtime pieces
-// (ensure_init, map_err).  The curve table is ecdsa_curves.hpp, included
-// here; the verification library is not linked.
+// (ensure_init, map_err).  The curve table is ecdsa_curves.hpp, parsed here
+// by ecdsa_host.hpp; the verification library is not linked.
 //
 // The window table of a curve's base point (60 KiB) is derived on the host
 // once per process and uploaded once per device, under a lock, with a
@@ -14,7 +14,8 @@
 // through page-locked memory on a private stream: copy -> H2D -> kernel ->
 // D2H -> copy, one chunk in flight.  After the last chunk every staging
 // buffer, page-locked and on the device, is overwritten with zeros: they held
-// private keys and nonces.  Nothing falls back to the CPU.
+// private keys and nonces (the staging context and its wipe() are
+// host_stage.hpp's).  Nothing falls back to the CPU.
 #include <errno.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -31,8 +32,9 @@
 
 #include "../../include/lcb_ecdsa_sign_gpu.h"
 #include "../../include/lcb_hash_gpu.h"
-#include "ecdsa_curves.hpp"
+#include "ecdsa_host.hpp"
 #include "ecdsa_sign_internal.hpp"
+#include "host_stage.hpp"
 #include "lcb_internal.hpp"
 
 using namespace lcbgpu;
@@ -40,39 +42,7 @@ using namespace lcbec;
 
 namespace {
 
-#define EC_TRY(expr)                              \
-    do {                                          \
-        hipError_t _e = (expr);                   \
-        if (_e != hipSuccess) return map_err(_e); \
-    } while (0)
-
-static_assert(kEinval == EINVAL, "the kernel's EINVAL is the host's");
 static_assert(sizeof(Table) == 8 * kLimbs * kWinEntries * 2 * kNumBytes, "the table is packed");
-
-// The curve table parsed and its Montgomery constants derived, once.
-struct CurveTable {
-    Curve<kLimbs> c[kCurveCount];
-    bool ok[kCurveCount];
-    CurveTable() {
-        for (int id = 0; id < kCurveCount; ++id) {
-            uint8_t raw[6 * kNumBytes];
-            for (int k = 0; k < 6; ++k)
-                for (int i = 0; i < kNumBytes; ++i) {
-                    auto nib = [](char ch) { return (uint8_t)(ch <= '9' ? ch - '0' : ch - 'a' + 10); };
-                    const char* h = kCurves[id].num[k] + 2 * i;
-                    raw[kNumBytes * k + i] = (uint8_t)(nib(h[0]) << 4 | nib(h[1]));
-                }
-            ok[id] = curve_setup(c[id], raw, kCurves[id].algo);
-        }
-    }
-};
-
-const CurveTable& table() {
-    static const CurveTable t;
-    return t;
-}
-
-bool known(int id) { return id >= 0 && id < kCurveCount && table().ok[id]; }
 
 // ------------------------------------------------------- the window tables
 std::mutex g_tables_mu;
@@ -82,7 +52,7 @@ std::map<std::pair<int, int>, Table*> g_dev_table;  // (device, curve) -> device
 // The window table of `curve` on the current device; uploads it on first use.
 int base_table(int curve, const Table** out) {
     int dev = 0;
-    EC_TRY(hipGetDevice(&dev));
+    LCB_HOST_TRY(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(g_tables_mu);
     auto it = g_dev_table.find({dev, curve});
     if (it == g_dev_table.end()) {
@@ -95,7 +65,7 @@ int base_table(int curve, const Table** out) {
             g_host_table[curve] = std::move(t);
         }
         Table* d = nullptr;
-        EC_TRY(hipMalloc(reinterpret_cast<void**>(&d), sizeof(Table)));
+        LCB_HOST_TRY(hipMalloc(reinterpret_cast<void**>(&d), sizeof(Table)));
         const hipError_t e = hipMemcpy(d, g_host_table[curve].get(), sizeof(Table), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             (void)hipFree(d);
@@ -108,71 +78,21 @@ int base_table(int curve, const Table** out) {
 }
 
 // ------------------------------------------------------------ host mode
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-struct SignStage {
-    int device = -1;
-    size_t cap = 0, kcap = 0;  // bytes per chunk / bytes of the key table
-    hipStream_t st = nullptr;
-    uint8_t *h = nullptr, *d = nullptr;    // one chunk: inputs | outputs | status
-    uint8_t *hk = nullptr, *dk = nullptr;  // the whole key table of a key_idx batch
-
-    void release() {
-        if (h) (void)hipHostFree(h);
-        if (hk) (void)hipHostFree(hk);
-        if (d) (void)hipFree(d);
-        if (dk) (void)hipFree(dk);
-        if (st) (void)hipStreamDestroy(st);
-        h = d = hk = dk = nullptr;
-        st = nullptr;
-        cap = kcap = 0;
-        device = -1;
-    }
-    ~SignStage() { release(); }
-
-    int ensure(int dev, size_t bytes, size_t key_bytes) {
-        if (device == dev && cap >= bytes && kcap >= key_bytes) return 0;
-        const size_t nb = std::max(bytes, cap), nk = std::max(key_bytes, kcap);
-        release();
-        device = dev;
-        EC_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        EC_TRY(hipHostMalloc(reinterpret_cast<void**>(&h), nb, hipHostMallocDefault));
-        EC_TRY(hipMalloc(reinterpret_cast<void**>(&d), nb));
-        if (nk) {
-            EC_TRY(hipHostMalloc(reinterpret_cast<void**>(&hk), nk, hipHostMallocDefault));
-            EC_TRY(hipMalloc(reinterpret_cast<void**>(&dk), nk));
-        }
-        cap = nb;
-        kcap = nk;
-        return 0;
-    }
-
-    // Zeros over everything a call staged (`bytes` of the chunk buffers,
-    // `key_bytes` of the key table), on the host and on the device; waits.
-    int wipe(size_t bytes, size_t key_bytes) {
-        hipError_t e = hipSuccess, e2;
-        if (h) memset(h, 0, std::min(bytes, cap));
-        if (hk) memset(hk, 0, std::min(key_bytes, kcap));
-        if (d && st && (e2 = hipMemsetAsync(d, 0, std::min(bytes, cap), st)) != hipSuccess) e = e2;
-        if (dk && st && key_bytes && (e2 = hipMemsetAsync(dk, 0, std::min(key_bytes, kcap), st)) != hipSuccess) e = e2;
-        if (st && (e2 = hipStreamSynchronize(st)) != hipSuccess) e = e2;
-        return e == hipSuccess ? 0 : map_err(e);
-    }
-};
-
-thread_local SignStage g_stage;
+// h / d: one chunk, inputs | outputs | status.  h2 / d2: the whole key table of a
+// key_idx batch.
+thread_local HostStage g_stage;
 constexpr size_t kChunkItems = 1u << 18;
 
 struct SignLayout {
     size_t chunk, o_rnd, o_priv, o_idx, o_sig, o_st, bytes, key_bytes;
 };
 
-int sign_chunks(SignStage& S, const SignLayout& y, const Curve<kLimbs>& c, const Table* t, int le,
+int sign_chunks(HostStage& S, const SignLayout& y, const Curve<kLimbs>& c, const Table* t, int le,
                 const uint8_t* hashes, size_t hash_size, const uint8_t* priv, size_t nkeys, const uint32_t* key_idx,
                 const uint8_t* rnd, size_t count, uint8_t* sigs, int32_t* status) {
     if (y.key_bytes) {
-        memcpy(S.hk, priv, y.key_bytes);
-        EC_TRY(hipMemcpyAsync(S.dk, S.hk, y.key_bytes, hipMemcpyHostToDevice, S.st));
+        memcpy(S.h2, priv, y.key_bytes);
+        LCB_HOST_TRY(hipMemcpyAsync(S.d2, S.h2, y.key_bytes, hipMemcpyHostToDevice, S.st));
     }
     for (size_t i = 0; i < count; i += y.chunk) {
         const size_t n = std::min(y.chunk, count - i);
@@ -182,11 +102,11 @@ int sign_chunks(SignStage& S, const SignLayout& y, const Curve<kLimbs>& c, const
             memcpy(S.h + y.o_idx, key_idx + i, n * 4);
         else
             memcpy(S.h + y.o_priv, priv + i * kNumBytes, n * kNumBytes);
-        EC_TRY(hipMemcpyAsync(S.d, S.h, y.o_sig, hipMemcpyHostToDevice, S.st));
+        LCB_HOST_TRY(hipMemcpyAsync(S.d, S.h, y.o_sig, hipMemcpyHostToDevice, S.st));
         SignArgs a;
         a.hashes = S.d;
         a.rnd = S.d + y.o_rnd;
-        a.priv = key_idx ? S.dk : S.d + y.o_priv;
+        a.priv = key_idx ? S.d2 : S.d + y.o_priv;
         a.key_idx = key_idx ? reinterpret_cast<const uint32_t*>(S.d + y.o_idx) : nullptr;
         a.sigs = S.d + y.o_sig;
         a.status = reinterpret_cast<int32_t*>(S.d + y.o_st);
@@ -195,9 +115,10 @@ int sign_chunks(SignStage& S, const SignLayout& y, const Curve<kLimbs>& c, const
         a.hash_size = (uint32_t)hash_size;
         a.le = le ? 1u : 0u;
         launch_ecdsa_sign(a, c, t, S.st);
-        EC_TRY(hipGetLastError());
-        EC_TRY(hipMemcpyAsync(S.h + y.o_sig, S.d + y.o_sig, y.o_st - y.o_sig + n * 4, hipMemcpyDeviceToHost, S.st));
-        EC_TRY(hipStreamSynchronize(S.st));
+        LCB_HOST_TRY(hipGetLastError());
+        LCB_HOST_TRY(
+            hipMemcpyAsync(S.h + y.o_sig, S.d + y.o_sig, y.o_st - y.o_sig + n * 4, hipMemcpyDeviceToHost, S.st));
+        LCB_HOST_TRY(hipStreamSynchronize(S.st));
         memcpy(sigs + i * 2 * kNumBytes, S.h + y.o_sig, n * 2 * kNumBytes);
         memcpy(status + i, S.h + y.o_st, n * 4);
     }
@@ -208,7 +129,7 @@ int sign_host(const Curve<kLimbs>& c, const Table* t, int le, const uint8_t* has
               const uint8_t* priv, size_t nkeys, const uint32_t* key_idx, const uint8_t* rnd, size_t count,
               uint8_t* sigs, int32_t* status) {
     int dev = 0;
-    EC_TRY(hipGetDevice(&dev));
+    LCB_HOST_TRY(hipGetDevice(&dev));
     SignLayout y;
     y.chunk = std::min(count, kChunkItems);
     y.o_rnd = up16(y.chunk * hash_size);
@@ -228,12 +149,12 @@ struct KeyLayout {
     size_t chunk, o_priv, o_pub, o_st, bytes;
 };
 
-int keys_chunks(SignStage& S, const KeyLayout& y, const Curve<kLimbs>& c, const Table* t, int le, bool from_rnd,
+int keys_chunks(HostStage& S, const KeyLayout& y, const Curve<kLimbs>& c, const Table* t, int le, bool from_rnd,
                 const uint8_t* in, size_t count, uint8_t* priv, uint8_t* pub, int32_t* status) {
     for (size_t i = 0; i < count; i += y.chunk) {
         const size_t n = std::min(y.chunk, count - i);
         memcpy(S.h, in + i * kNumBytes, n * kNumBytes);
-        EC_TRY(hipMemcpyAsync(S.d, S.h, n * kNumBytes, hipMemcpyHostToDevice, S.st));
+        LCB_HOST_TRY(hipMemcpyAsync(S.d, S.h, n * kNumBytes, hipMemcpyHostToDevice, S.st));
         KeyArgs a;
         a.in = S.d;
         a.priv = from_rnd ? S.d + y.o_priv : nullptr;
@@ -243,9 +164,10 @@ int keys_chunks(SignStage& S, const KeyLayout& y, const Curve<kLimbs>& c, const 
         a.from_rnd = from_rnd ? 1u : 0u;
         a.le = le ? 1u : 0u;
         launch_ecdsa_keys(a, c, t, S.st);
-        EC_TRY(hipGetLastError());
-        EC_TRY(hipMemcpyAsync(S.h + y.o_priv, S.d + y.o_priv, y.o_st - y.o_priv + n * 4, hipMemcpyDeviceToHost, S.st));
-        EC_TRY(hipStreamSynchronize(S.st));
+        LCB_HOST_TRY(hipGetLastError());
+        LCB_HOST_TRY(
+            hipMemcpyAsync(S.h + y.o_priv, S.d + y.o_priv, y.o_st - y.o_priv + n * 4, hipMemcpyDeviceToHost, S.st));
+        LCB_HOST_TRY(hipStreamSynchronize(S.st));
         if (from_rnd) memcpy(priv + i * kNumBytes, S.h + y.o_priv, n * kNumBytes);
         memcpy(pub + i * 2 * kNumBytes, S.h + y.o_pub, n * 2 * kNumBytes);
         memcpy(status + i, S.h + y.o_st, n * 4);
@@ -256,7 +178,7 @@ int keys_chunks(SignStage& S, const KeyLayout& y, const Curve<kLimbs>& c, const 
 int keys_host(const Curve<kLimbs>& c, const Table* t, int le, bool from_rnd, const uint8_t* in, size_t count,
               uint8_t* priv, uint8_t* pub, int32_t* status) {
     int dev = 0;
-    EC_TRY(hipGetDevice(&dev));
+    LCB_HOST_TRY(hipGetDevice(&dev));
     KeyLayout y;
     y.chunk = std::min(count, kChunkItems);
     y.o_priv = y.chunk * kNumBytes;

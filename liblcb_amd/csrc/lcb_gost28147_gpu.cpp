@@ -8,8 +8,8 @@
 // the packed table travel as kernel arguments, so the caller's arrays are
 // free when the call returns.  Host mode stages chunk by chunk through
 // page-locked memory on a private stream: pack -> H2D -> kernel -> D2H ->
-// scatter.  It is NOT pipelined (one chunk in flight).  Nothing falls back
-// to the CPU.
+// scatter.  It is NOT pipelined (one chunk in flight); the staging context
+// and the chunk size are host_stage.hpp's.  Nothing falls back to the CPU.
 #include <errno.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -23,18 +23,13 @@
 #include "../../include/lcb_gost28147_gpu.h"
 #include "../../include/lcb_hash_gpu.h"
 #include "gost28147_internal.hpp"
+#include "host_stage.hpp"
 #include "lcb_internal.hpp"
 
 using namespace lcbgpu;
 using namespace lcbgost;
 
 namespace {
-
-#define GOST_TRY(expr)                            \
-    do {                                          \
-        hipError_t _e = (expr);                   \
-        if (_e != hipSuccess) return map_err(_e); \
-    } while (0)
 
 // The six parameter sets of gost28147.h:74-139 (RFC 4357 section 11.1-11.2,
 // GOST R 34.11-94 test set, TC26 "Z"), one string of 16 nibbles per row.
@@ -127,7 +122,7 @@ int gost_enqueue(GostArgs a, const GostTable& t, bool mac, hipStream_t s) {
     }
     const uint64_t nparts = (a.count + 1023) / 1024;
     uint8_t* scratch = nullptr;
-    GOST_TRY(scratch_alloc(reinterpret_cast<void**>(&scratch), 1024 + (scan ? (nparts + a.count + 1) * 8 : 0), s));
+    LCB_HOST_TRY(scratch_alloc(reinterpret_cast<void**>(&scratch), 1024 + (scan ? (nparts + a.count + 1) * 8 : 0), s));
     uint32_t* dtable = reinterpret_cast<uint32_t*>(scratch);
     uint64_t* parts = reinterpret_cast<uint64_t*>(scratch + 1024);
     launch_gost_table(t, dtable, s);
@@ -142,64 +137,21 @@ int gost_enqueue(GostArgs a, const GostTable& t, bool mac, hipStream_t s) {
 }
 
 // ------------------------------------------------------------ host mode
-struct GostStage {
-    int device = -1;
-    size_t cap = 0, mcap = 0;  // data bytes / buffers per chunk
-    hipStream_t st = nullptr;
-    uint8_t *h_data = nullptr, *d_data = nullptr;  // the kernel runs in place
-    uint8_t *h_meta = nullptr, *d_meta = nullptr;  // offsets | lengths, then MACs (8 per buffer)
+// h / d: the packed data of one chunk (the kernel runs in place).  h2 / d2:
+// offsets | lengths, then MACs (8 per buffer).
+size_t meta_bytes(size_t m) { return m * (8 + 4 + 8) + 16; }
 
-    static size_t meta_bytes(size_t m) { return m * (8 + 4 + 8) + 16; }
-
-    void release() {
-        if (h_data) (void)hipHostFree(h_data);
-        if (h_meta) (void)hipHostFree(h_meta);
-        if (d_data) (void)hipFree(d_data);
-        if (d_meta) (void)hipFree(d_meta);
-        if (st) (void)hipStreamDestroy(st);
-        h_data = h_meta = d_data = d_meta = nullptr;
-        st = nullptr;
-        cap = mcap = 0;
-        device = -1;
-    }
-    ~GostStage() { release(); }
-
-    int ensure(int dev, size_t need_bytes, size_t need_msgs) {
-        if (device == dev && cap >= need_bytes && mcap >= need_msgs) return 0;
-        const size_t nb = std::max(need_bytes, cap), nm = std::max(need_msgs, mcap);
-        release();
-        device = dev;
-        GOST_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        GOST_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_data), nb, hipHostMallocDefault));
-        GOST_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_meta), meta_bytes(nm), hipHostMallocDefault));
-        GOST_TRY(hipMalloc(reinterpret_cast<void**>(&d_data), nb));
-        GOST_TRY(hipMalloc(reinterpret_cast<void**>(&d_meta), meta_bytes(nm)));
-        cap = nb;
-        mcap = nm;
-        return 0;
-    }
-};
-
-thread_local GostStage g_stage;
+thread_local HostStage g_stage;
 constexpr size_t kChunkMsgs = 1u << 18;
 
-// Staging bytes per chunk; LCB_GOST28147_CHUNK_BYTES overrides it (tests
-// force a batch across a chunk boundary with it).
-size_t chunk_bytes() {
-    size_t v = 64ull << 20;
-    if (const char* e = getenv("LCB_GOST28147_CHUNK_BYTES")) {
-        const unsigned long long x = strtoull(e, nullptr, 0);
-        if (x) v = (size_t)x;
-    }
-    return std::max<size_t>(v, 64);
-}
-
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+// Overrides the staging bytes per chunk (tests force a batch across a chunk
+// boundary with it).
+constexpr const char* kChunkEnv = "LCB_GOST28147_CHUNK_BYTES";
 
 int gost_host(const Setup& su, bool mac, const uint8_t* src, uint8_t* dst, const uint64_t* offsets,
               const uint32_t* lengths, size_t count, uint64_t stride, uint32_t fixed_len, size_t mac_size) {
     int dev = 0;
-    GOST_TRY(hipGetDevice(&dev));
+    LCB_HOST_TRY(hipGetDevice(&dev));
     auto off_of = [&](size_t i) -> uint64_t { return offsets ? offsets[i] : (uint64_t)i * stride; };
     // Only a buffer's whole blocks are staged: the tail is neither read nor written.
     auto used_of = [&](size_t i) -> size_t { return (size_t)((lengths ? lengths[i] : fixed_len) & ~7u); };
@@ -209,29 +161,32 @@ int gost_host(const Setup& su, bool mac, const uint8_t* src, uint8_t* dst, const
         for (size_t i = 0; i < count; ++i) maxlen = std::max<size_t>(maxlen, lengths[i]);
     }
     // The chunk limit of THIS call (the staging buffers only ever grow).
-    const size_t limit = std::max(chunk_bytes(), up16(maxlen));
-    if (int rc = g_stage.ensure(dev, limit, std::min(count, kChunkMsgs))) return rc;
-    GostStage& S = g_stage;
+    const size_t limit = std::max(chunk_bytes(kChunkEnv, 64), up16(maxlen));
+    // Buffers per chunk: the stage's second pair is sized in bytes, so a chunk's
+    // metadata has to fit meta_bytes(max_msgs).
+    const size_t max_msgs = std::min(count, kChunkMsgs);
+    if (int rc = g_stage.ensure(dev, limit, meta_bytes(max_msgs))) return rc;
+    HostStage& S = g_stage;
     std::vector<Piece> pieces;
     size_t i = 0;
     while (i < count) {
         // Buffers [i, j), each packed at a 16-byte boundary, that fit one chunk.
         size_t j = i, total = 0;
-        while (j < count && j - i < S.mcap) {
+        while (j < count && j - i < max_msgs) {
             const size_t n = up16(used_of(j));
             if (j > i && total + n > limit) break;
             total += n;
             ++j;
         }
         const size_t n = j - i;
-        uint64_t* h_off = reinterpret_cast<uint64_t*>(S.h_meta);
-        uint32_t* h_len = reinterpret_cast<uint32_t*>(S.h_meta + n * 8);
+        uint64_t* h_off = reinterpret_cast<uint64_t*>(S.h2);
+        uint32_t* h_len = reinterpret_cast<uint32_t*>(S.h2 + n * 8);
         const size_t mac_at = up16(n * 12);
         pieces.clear();
         size_t pos = 0, bytes = 0;
         for (size_t k = 0; k < n; ++k) {
             const size_t u = used_of(i + k);
-            if (u) pieces.push_back(Piece{S.h_data + pos, src + off_of(i + k), u});
+            if (u) pieces.push_back(Piece{S.h + pos, src + off_of(i + k), u});
             h_off[k] = pos;
             h_len[k] = (uint32_t)u;
             pos += up16(u);
@@ -240,30 +195,30 @@ int gost_host(const Setup& su, bool mac, const uint8_t* src, uint8_t* dst, const
         parallel_copy(pieces, bytes);
         GostArgs a = su.a;
         a.count = n;
-        a.src = S.d_data;
-        a.dst = mac ? S.d_meta + mac_at : S.d_data;
+        a.src = S.d;
+        a.dst = mac ? S.d2 + mac_at : S.d;
         a.mac_size = (uint32_t)mac_size;
         if (lengths) {
-            a.offsets = reinterpret_cast<const uint64_t*>(S.d_meta);
-            a.lengths = reinterpret_cast<const uint32_t*>(S.d_meta + n * 8);
-            GOST_TRY(hipMemcpyAsync(S.d_meta, S.h_meta, n * 12, hipMemcpyHostToDevice, S.st));
+            a.offsets = reinterpret_cast<const uint64_t*>(S.d2);
+            a.lengths = reinterpret_cast<const uint32_t*>(S.d2 + n * 8);
+            LCB_HOST_TRY(hipMemcpyAsync(S.d2, S.h2, n * 12, hipMemcpyHostToDevice, S.st));
         } else {
             a.stride = up16(used_of(0));
             a.fixed_len = (uint32_t)used_of(0);
         }
-        if (pos) GOST_TRY(hipMemcpyAsync(S.d_data, S.h_data, pos, hipMemcpyHostToDevice, S.st));
+        if (pos) LCB_HOST_TRY(hipMemcpyAsync(S.d, S.h, pos, hipMemcpyHostToDevice, S.st));
         if (int rc = gost_enqueue(a, su.t, mac, S.st)) return rc;
         if (mac)
-            GOST_TRY(hipMemcpyAsync(S.h_meta + mac_at, S.d_meta + mac_at, n * mac_size, hipMemcpyDeviceToHost, S.st));
+            LCB_HOST_TRY(hipMemcpyAsync(S.h2 + mac_at, S.d2 + mac_at, n * mac_size, hipMemcpyDeviceToHost, S.st));
         else if (pos)
-            GOST_TRY(hipMemcpyAsync(S.h_data, S.d_data, pos, hipMemcpyDeviceToHost, S.st));
-        GOST_TRY(hipStreamSynchronize(S.st));
+            LCB_HOST_TRY(hipMemcpyAsync(S.h, S.d, pos, hipMemcpyDeviceToHost, S.st));
+        LCB_HOST_TRY(hipStreamSynchronize(S.st));
         if (mac) {
-            memcpy(dst + i * mac_size, S.h_meta + mac_at, n * mac_size);
+            memcpy(dst + i * mac_size, S.h2 + mac_at, n * mac_size);
         } else {
             pieces.clear();
             for (size_t k = 0; k < n; ++k)
-                if (h_len[k]) pieces.push_back(Piece{dst + off_of(i + k), S.h_data + h_off[k], h_len[k]});
+                if (h_len[k]) pieces.push_back(Piece{dst + off_of(i + k), S.h + h_off[k], h_len[k]});
             parallel_copy(pieces, bytes);
         }
         i = j;

@@ -10,7 +10,9 @@
 // waits for the device first (the set's earlier device-mode work, its
 // creation included, may still be queued on the caller's streams), then
 // stages chunk by chunk through page-locked memory on the set's own stream
-// and waits; it is NOT pipelined.  Nothing falls back to the CPU.
+// and waits; it is NOT pipelined.  The staging buffers belong to the set (not
+// host_stage.hpp's per-thread context; the error macro, up16 and the chunk
+// size are taken from there).  Nothing falls back to the CPU.
 #include <errno.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -24,6 +26,7 @@
 
 #include "../../include/lcb_hash_gpu.h"
 #include "../../include/lcb_hash_stream_gpu.h"
+#include "host_stage.hpp"
 #include "lcb_internal.hpp"
 #include "stream_internal.hpp"
 #include "stream_state.hpp"
@@ -31,31 +34,16 @@
 using namespace lcbgpu;
 using namespace lcbstream;
 
-#define STREAM_TRY(expr)                          \
-    do {                                          \
-        hipError_t _e = (expr);                   \
-        if (_e != hipSuccess) return map_err(_e); \
-    } while (0)
-
 namespace {
-
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 constexpr size_t kInitWords = 128;   // init image (<= kMaxWords), padded
 constexpr size_t kOpadWords = 64;    // opad state (<= 48)
 constexpr size_t kBadWords = 64;     // the check's flag word, in a line of its own
 constexpr size_t kChunkMsgs = 1u << 18;
 
-// Staging bytes per chunk; LCB_HASH_STREAM_CHUNK_BYTES overrides it (tests
-// force an update across a chunk boundary with it).
-size_t chunk_bytes() {
-    size_t v = 64ull << 20;
-    if (const char* e = getenv("LCB_HASH_STREAM_CHUNK_BYTES")) {
-        const unsigned long long x = strtoull(e, nullptr, 0);
-        if (x) v = (size_t)x;
-    }
-    return std::max<size_t>(v, 64);
-}
+// Overrides the staging bytes per chunk (tests force an update across a chunk
+// boundary with it).
+constexpr const char* kChunkEnv = "LCB_HASH_STREAM_CHUNK_BYTES";
 
 // The current device set to a set's for one call.
 struct DevGuard {
@@ -83,7 +71,9 @@ struct lcb_hash_stream_set_s {
     hipEvent_t ev = nullptr;
     uint32_t epoch = 0;
     std::vector<uint8_t> seen;       // host-side index check
-    // host mode and export / import
+    // host mode and export / import.  Not the HostStage of host_stage.hpp:
+    // this staging belongs to a set, not to a thread, its stream outlives the
+    // buffers, and its sizes are clamped to non-zero.
     hipStream_t st = nullptr;
     size_t cap = 0, mcap = 0;        // staged data bytes / entries
     uint8_t *h_data = nullptr, *d_data = nullptr;
@@ -108,14 +98,14 @@ struct lcb_hash_stream_set_s {
     }
 
     int stage_ensure(size_t need_bytes, size_t need_msgs) {
-        if (!st) STREAM_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        if (!st) LCB_HOST_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         if (cap >= need_bytes && mcap >= need_msgs && h_meta) return 0;
         const size_t nb = std::max<size_t>(std::max(need_bytes, cap), 64), nm = std::max<size_t>(std::max(need_msgs, mcap), 1);
         stage_release();
-        STREAM_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_data), nb, hipHostMallocDefault));
-        STREAM_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_meta), meta_bytes(nm), hipHostMallocDefault));
-        STREAM_TRY(hipMalloc(reinterpret_cast<void**>(&d_data), nb));
-        STREAM_TRY(hipMalloc(reinterpret_cast<void**>(&d_meta), meta_bytes(nm)));
+        LCB_HOST_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_data), nb, hipHostMallocDefault));
+        LCB_HOST_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_meta), meta_bytes(nm), hipHostMallocDefault));
+        LCB_HOST_TRY(hipMalloc(reinterpret_cast<void**>(&d_data), nb));
+        LCB_HOST_TRY(hipMalloc(reinterpret_cast<void**>(&d_meta), meta_bytes(nm)));
         cap = nb;
         mcap = nm;
         return 0;
@@ -143,7 +133,7 @@ typedef lcb_hash_stream_set_s Set;
 // 32-bit counter wraps.
 int next_epoch(Set* set, hipStream_t s, uint32_t* out) {
     if (++set->epoch == 0) {
-        STREAM_TRY(hipMemsetAsync(set->bad, 0, (kBadWords + set->nstreams) * 4, s));
+        LCB_HOST_TRY(hipMemsetAsync(set->bad, 0, (kBadWords + set->nstreams) * 4, s));
         set->epoch = 1;
     }
     *out = set->epoch;
@@ -158,14 +148,14 @@ int run_device(Set* set, StreamArgs a, hipStream_t s, F launch) {
         if (int rc = next_epoch(set, s, &a.epoch)) return rc;
         a.bad = set->bad;
         launch_stream_check(a, s);
-        STREAM_TRY(hipGetLastError());
-        STREAM_TRY(hipMemcpyAsync(set->bad_host, set->bad, 4, hipMemcpyDeviceToHost, s));
-        STREAM_TRY(hipEventRecord(set->ev, s));
+        LCB_HOST_TRY(hipGetLastError());
+        LCB_HOST_TRY(hipMemcpyAsync(set->bad_host, set->bad, 4, hipMemcpyDeviceToHost, s));
+        LCB_HOST_TRY(hipEventRecord(set->ev, s));
     }
     launch(a, s);
     const hipError_t e = hipGetLastError();
     if (check) {
-        STREAM_TRY(hipEventSynchronize(set->ev));
+        LCB_HOST_TRY(hipEventSynchronize(set->ev));
         if (*set->bad_host == a.epoch) return EINVAL;
     }
     return map_err(e);
@@ -187,7 +177,7 @@ int host_index_check(Set* set, const uint32_t* index, size_t count) {
 // staging buffers.
 int host_simple(Set* set, const uint32_t* index, size_t count, uint8_t* digests, bool keep) {
     if (int rc = host_index_check(set, index, count)) return rc;
-    STREAM_TRY(hipDeviceSynchronize());   // behind whatever the caller's streams still hold for this set
+    LCB_HOST_TRY(hipDeviceSynchronize());   // behind whatever the caller's streams still hold for this set
     if (int rc = set->stage_ensure(0, count)) return rc;
     const size_t D = dsize(set->alg);
     StreamArgs a = set->args();
@@ -195,7 +185,7 @@ int host_simple(Set* set, const uint32_t* index, size_t count, uint8_t* digests,
     uint8_t* d_dig = set->d_meta + up16(count * 4);
     if (index) {
         memcpy(set->h_meta, index, count * 4);
-        STREAM_TRY(hipMemcpyAsync(set->d_meta, set->h_meta, count * 4, hipMemcpyHostToDevice, set->st));
+        LCB_HOST_TRY(hipMemcpyAsync(set->d_meta, set->h_meta, count * 4, hipMemcpyHostToDevice, set->st));
         a.index = reinterpret_cast<const uint32_t*>(set->d_meta);
     }
     if (digests) {
@@ -205,10 +195,10 @@ int host_simple(Set* set, const uint32_t* index, size_t count, uint8_t* digests,
     } else {
         launch_stream_fill(a, set->st);
     }
-    STREAM_TRY(hipGetLastError());
+    LCB_HOST_TRY(hipGetLastError());
     uint8_t* h_dig = set->h_meta + up16(count * 4);
-    if (digests) STREAM_TRY(hipMemcpyAsync(h_dig, d_dig, count * D, hipMemcpyDeviceToHost, set->st));
-    STREAM_TRY(hipStreamSynchronize(set->st));
+    if (digests) LCB_HOST_TRY(hipMemcpyAsync(h_dig, d_dig, count * D, hipMemcpyDeviceToHost, set->st));
+    LCB_HOST_TRY(hipStreamSynchronize(set->st));
     if (digests) memcpy(digests, h_dig, count * D);
     return 0;
 }
@@ -216,11 +206,11 @@ int host_simple(Set* set, const uint32_t* index, size_t count, uint8_t* digests,
 int host_update(Set* set, const uint32_t* index, const uint8_t* data, const uint64_t* offsets,
                 const uint32_t* lengths, size_t count, uint64_t stride, uint32_t fixed_len) {
     if (int rc = host_index_check(set, index, count)) return rc;
-    STREAM_TRY(hipDeviceSynchronize());   // behind whatever the caller's streams still hold for this set
+    LCB_HOST_TRY(hipDeviceSynchronize());   // behind whatever the caller's streams still hold for this set
     auto off_of = [&](size_t i) -> uint64_t { return offsets ? offsets[i] : (uint64_t)i * stride; };
     auto len_of = [&](size_t i) -> size_t { return lengths ? lengths[i] : fixed_len; };
     size_t maxlen = 0, sum = 0;
-    const size_t limit0 = chunk_bytes();
+    const size_t limit0 = chunk_bytes(kChunkEnv, 64);
     for (size_t i = 0; i < count; ++i) {
         maxlen = std::max(maxlen, len_of(i));
         sum += up16(len_of(i));
@@ -261,11 +251,11 @@ int host_update(Set* set, const uint32_t* index, const uint8_t* data, const uint
         a.offsets = reinterpret_cast<const uint64_t*>(set->d_meta);
         a.lengths = reinterpret_cast<const uint32_t*>(set->d_meta + n * 8);
         a.index = reinterpret_cast<const uint32_t*>(set->d_meta + n * 12);
-        STREAM_TRY(hipMemcpyAsync(set->d_meta, set->h_meta, n * 16, hipMemcpyHostToDevice, set->st));
-        if (pos) STREAM_TRY(hipMemcpyAsync(set->d_data, set->h_data, pos, hipMemcpyHostToDevice, set->st));
+        LCB_HOST_TRY(hipMemcpyAsync(set->d_meta, set->h_meta, n * 16, hipMemcpyHostToDevice, set->st));
+        if (pos) LCB_HOST_TRY(hipMemcpyAsync(set->d_data, set->h_data, pos, hipMemcpyHostToDevice, set->st));
         launch_stream_update(set->alg, a, set->st);
-        STREAM_TRY(hipGetLastError());
-        STREAM_TRY(hipStreamSynchronize(set->st));
+        LCB_HOST_TRY(hipGetLastError());
+        LCB_HOST_TRY(hipStreamSynchronize(set->st));
         i = j;
     }
     return 0;
@@ -293,7 +283,7 @@ int lcb_hash_stream_create(int alg, const uint8_t* key, size_t key_len, size_t n
         return rc;
     };
     auto build = [&]() -> int {
-        STREAM_TRY(hipGetDevice(&set->device));
+        LCB_HOST_TRY(hipGetDevice(&set->device));
         set->alg = alg;
         set->nstreams = nstreams;
         set->keyed = key != nullptr;
@@ -301,21 +291,21 @@ int lcb_hash_stream_create(int alg, const uint8_t* key, size_t key_len, size_t n
         set->pitch = (nstreams + 63) & ~(uint64_t)63;
         const size_t head = kInitWords + kOpadWords + kBadWords;
         const size_t total = head + set->pitch + (size_t)set->words * set->pitch;
-        STREAM_TRY(hipMalloc(reinterpret_cast<void**>(&set->dmem), total * 4));
+        LCB_HOST_TRY(hipMalloc(reinterpret_cast<void**>(&set->dmem), total * 4));
         set->init = set->dmem;
         set->opad = set->init + kInitWords;
         set->bad = set->opad + kOpadWords;
         set->stamp = set->bad + kBadWords;
         set->ctx = set->stamp + set->pitch;
-        STREAM_TRY(hipHostMalloc(reinterpret_cast<void**>(&set->bad_host), 64, hipHostMallocDefault));
+        LCB_HOST_TRY(hipHostMalloc(reinterpret_cast<void**>(&set->bad_host), 64, hipHostMallocDefault));
         *set->bad_host = 0;
-        STREAM_TRY(hipEventCreateWithFlags(&set->ev, hipEventDisableTiming));
-        STREAM_TRY(hipMemsetAsync(set->dmem, 0, (head + set->pitch) * 4, s));
+        LCB_HOST_TRY(hipEventCreateWithFlags(&set->ev, hipEventDisableTiming));
+        LCB_HOST_TRY(hipMemsetAsync(set->dmem, 0, (head + set->pitch) * 4, s));
         // The key travels through stream-ordered scratch, zeroed before it goes back.
         uint8_t* dkey = nullptr;
         const size_t kb = up16(key_len) + 16;
         if (set->keyed) {
-            STREAM_TRY(scratch_alloc(reinterpret_cast<void**>(&dkey), kb, s));
+            LCB_HOST_TRY(scratch_alloc(reinterpret_cast<void**>(&dkey), kb, s));
             hipError_t e = hipMemsetAsync(dkey, 0, kb, s);
             if (e == hipSuccess && key_len) {
                 std::vector<uint8_t> img(key, key + key_len);   // pageable: the copy returns once the bytes are staged
@@ -338,7 +328,7 @@ int lcb_hash_stream_create(int alg, const uint8_t* key, size_t key_len, size_t n
         StreamArgs a = set->args();
         a.count = nstreams;
         launch_stream_fill(a, s);
-        STREAM_TRY(hipGetLastError());
+        LCB_HOST_TRY(hipGetLastError());
         return 0;
     };
     if (int rc = build()) return fail(rc);
@@ -417,7 +407,7 @@ int lcb_hash_stream_export(lcb_hash_stream_set_p set, const uint32_t* stream_ind
     if (!states) return EINVAL;
     if (int rc = host_index_check(set, stream_index, count)) return rc;
     DevGuard g(set->device);
-    STREAM_TRY(hipDeviceSynchronize());
+    LCB_HOST_TRY(hipDeviceSynchronize());
     const size_t W = set->words;
     for (size_t i = 0; i < count;) {
         const size_t n = std::min(count - i, kChunkMsgs);
@@ -428,12 +418,12 @@ int lcb_hash_stream_export(lcb_hash_stream_set_p set, const uint32_t* stream_ind
         const uint32_t* h_img = reinterpret_cast<const uint32_t*>(set->h_meta + up16(n * 4));
         uint32_t* h_idx = reinterpret_cast<uint32_t*>(set->h_meta);
         for (size_t k = 0; k < n; ++k) h_idx[k] = stream_index ? stream_index[i + k] : (uint32_t)(i + k);
-        STREAM_TRY(hipMemcpyAsync(set->d_meta, set->h_meta, n * 4, hipMemcpyHostToDevice, set->st));
+        LCB_HOST_TRY(hipMemcpyAsync(set->d_meta, set->h_meta, n * 4, hipMemcpyHostToDevice, set->st));
         a.index = reinterpret_cast<const uint32_t*>(set->d_meta);
         launch_stream_gather(a, d_img, set->st);
-        STREAM_TRY(hipGetLastError());
-        STREAM_TRY(hipMemcpyAsync(set->h_meta + up16(n * 4), d_img, n * W * 4, hipMemcpyDeviceToHost, set->st));
-        STREAM_TRY(hipStreamSynchronize(set->st));
+        LCB_HOST_TRY(hipGetLastError());
+        LCB_HOST_TRY(hipMemcpyAsync(set->h_meta + up16(n * 4), d_img, n * W * 4, hipMemcpyDeviceToHost, set->st));
+        LCB_HOST_TRY(hipStreamSynchronize(set->st));
         for (size_t k = 0; k < n; ++k) words_to_state(set->alg, h_img + k * W, states[i + k]);
         i += n;
     }
@@ -449,7 +439,7 @@ int lcb_hash_stream_import(lcb_hash_stream_set_p set, const uint32_t* stream_ind
         if (int rc = state_check(set->alg, states[i])) return rc;
     if (int rc = host_index_check(set, stream_index, count)) return rc;
     DevGuard g(set->device);
-    STREAM_TRY(hipDeviceSynchronize());
+    LCB_HOST_TRY(hipDeviceSynchronize());
     const size_t W = set->words;
     for (size_t i = 0; i < count;) {
         const size_t n = std::min(count - i, kChunkMsgs);
@@ -463,11 +453,11 @@ int lcb_hash_stream_import(lcb_hash_stream_set_p set, const uint32_t* stream_ind
             state_to_words(set->alg, states[i + k], h_img + k * W);
         }
         const size_t bytes = up16(n * 4) + n * W * 4;
-        STREAM_TRY(hipMemcpyAsync(set->d_meta, set->h_meta, bytes, hipMemcpyHostToDevice, set->st));
+        LCB_HOST_TRY(hipMemcpyAsync(set->d_meta, set->h_meta, bytes, hipMemcpyHostToDevice, set->st));
         a.index = reinterpret_cast<const uint32_t*>(set->d_meta);
         launch_stream_scatter(a, reinterpret_cast<const uint32_t*>(set->d_meta + up16(n * 4)), set->st);
-        STREAM_TRY(hipGetLastError());
-        STREAM_TRY(hipStreamSynchronize(set->st));
+        LCB_HOST_TRY(hipGetLastError());
+        LCB_HOST_TRY(hipStreamSynchronize(set->st));
         i += n;
     }
     return 0;

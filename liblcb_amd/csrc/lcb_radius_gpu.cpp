@@ -15,8 +15,9 @@
 //
 // Both keyed passes run over all `count` packets with a device-written length
 // array that is 0 for a packet not in that pass.  Host mode stages chunk by
-// chunk through page-locked memory on a private stream and runs the same
-// sequence; it is NOT pipelined.  Nothing falls back to the CPU.
+// chunk through page-locked memory on a private stream (the staging context
+// and the chunk size are host_stage.hpp's) and runs the same sequence; it is
+// NOT pipelined.  Nothing falls back to the CPU.
 #include <errno.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -29,6 +30,7 @@
 
 #include "../../include/lcb_hash_gpu.h"
 #include "../../include/lcb_radius_gpu.h"
+#include "host_stage.hpp"
 #include "lcb_internal.hpp"
 #include "radius_internal.hpp"
 
@@ -36,14 +38,6 @@ using namespace lcbgpu;
 using namespace lcbrad;
 
 namespace {
-
-#define RAD_TRY(expr)                             \
-    do {                                          \
-        hipError_t _e = (expr);                   \
-        if (_e != hipSuccess) return map_err(_e); \
-    } while (0)
-
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // The caller's key table (host memory), checked once per call.
 struct KeyTab {
@@ -78,7 +72,7 @@ int rad_enqueue(RadArgs a, bool sign, const KeyTab& kt, hipStream_t s) {
     const size_t blob_b = up16(kt.total + 4), tab_b = up16(kt.nkeys * 4);
     const size_t key_b = blob_b + 2 * tab_b;
     uint8_t* d = nullptr;
-    RAD_TRY(scratch_alloc(reinterpret_cast<void**>(&d), side_b + key_b, s));
+    LCB_HOST_TRY(scratch_alloc(reinterpret_cast<void**>(&d), side_b + key_b, s));
     a.rec = reinterpret_cast<RadRec*>(d);
     a.park = reinterpret_cast<uint4*>(d + n * sizeof(RadRec));
     a.dig = a.park + 2 * n;
@@ -146,57 +140,16 @@ int rad_enqueue(RadArgs a, bool sign, const KeyTab& kt, hipStream_t s) {
 }
 
 // ------------------------------------------------------------ host mode
-struct RadStage {
-    int device = -1;
-    size_t cap = 0, mcap = 0;  // packet bytes / packets per chunk
-    hipStream_t st = nullptr;
-    uint8_t *h_data = nullptr, *d_data = nullptr;
-    uint8_t *h_meta = nullptr, *d_meta = nullptr;  // offsets | buf_sizes | key_index | errors | req_hdrs
+// h / d: the packed packets of one chunk.  h2 / d2: offsets | buf_sizes |
+// key_index | errors | req_hdrs.
+size_t meta_bytes(size_t m) { return m * (8 + 4 + 4 + 4 + 20) + 16; }
 
-    static size_t meta_bytes(size_t m) { return m * (8 + 4 + 4 + 4 + 20) + 16; }
-
-    void release() {
-        if (h_data) (void)hipHostFree(h_data);
-        if (h_meta) (void)hipHostFree(h_meta);
-        if (d_data) (void)hipFree(d_data);
-        if (d_meta) (void)hipFree(d_meta);
-        if (st) (void)hipStreamDestroy(st);
-        h_data = h_meta = d_data = d_meta = nullptr;
-        st = nullptr;
-        cap = mcap = 0;
-        device = -1;
-    }
-    ~RadStage() { release(); }
-
-    int ensure(int dev, size_t need_bytes, size_t need_msgs) {
-        if (device == dev && cap >= need_bytes && mcap >= need_msgs) return 0;
-        const size_t nb = std::max(need_bytes, cap), nm = std::max(need_msgs, mcap);
-        release();
-        device = dev;
-        RAD_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        RAD_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_data), nb, hipHostMallocDefault));
-        RAD_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_meta), meta_bytes(nm), hipHostMallocDefault));
-        RAD_TRY(hipMalloc(reinterpret_cast<void**>(&d_data), nb));
-        RAD_TRY(hipMalloc(reinterpret_cast<void**>(&d_meta), meta_bytes(nm)));
-        cap = nb;
-        mcap = nm;
-        return 0;
-    }
-};
-
-thread_local RadStage g_stage;
+thread_local HostStage g_stage;
 constexpr size_t kChunkMsgs = 1u << 18;
 
-// Staging bytes per chunk; LCB_RADIUS_CHUNK_BYTES overrides it (tests force a
-// batch across a chunk boundary with it).
-size_t chunk_bytes() {
-    size_t v = 64ull << 20;
-    if (const char* e = getenv("LCB_RADIUS_CHUNK_BYTES")) {
-        const unsigned long long x = strtoull(e, nullptr, 0);
-        if (x) v = (size_t)x;
-    }
-    return std::max<size_t>(v, kPktMax);
-}
+// Overrides the staging bytes per chunk (tests force a batch across a chunk
+// boundary with it).
+constexpr const char* kChunkEnv = "LCB_RADIUS_CHUNK_BYTES";
 
 // The bytes of a host packet buffer that are staged: [0, Length) where the
 // header can be read and Length fits, else just enough for the device guard
@@ -211,35 +164,39 @@ uint32_t staged_size(const uint8_t* p, uint32_t buf_size) {
 
 int rad_host(RadArgs u, bool sign, const KeyTab& kt) {
     int dev = 0;
-    RAD_TRY(hipGetDevice(&dev));
+    LCB_HOST_TRY(hipGetDevice(&dev));
     const size_t count = u.count;
     auto off_of = [&](size_t i) -> uint64_t { return u.offsets ? u.offsets[i] : (uint64_t)i * u.stride; };
     auto size_of = [&](size_t i) -> uint32_t { return u.buf_sizes ? u.buf_sizes[i] : u.fixed_size; };
     // The chunk limit of THIS call (the staging buffers only ever grow).
-    const size_t limit = std::max<size_t>(std::min<uint64_t>(chunk_bytes(), (uint64_t)count * kPktMax), kPktMax);
-    if (int rc = g_stage.ensure(dev, limit, std::min(count, kChunkMsgs))) return rc;
-    RadStage& S = g_stage;
+    const size_t limit =
+        std::max<size_t>(std::min<uint64_t>(chunk_bytes(kChunkEnv, kPktMax), (uint64_t)count * kPktMax), kPktMax);
+    // Packets per chunk: the stage's second pair is sized in bytes, so a chunk's
+    // metadata has to fit meta_bytes(max_msgs).
+    const size_t max_msgs = std::min(count, kChunkMsgs);
+    if (int rc = g_stage.ensure(dev, limit, meta_bytes(max_msgs))) return rc;
+    HostStage& S = g_stage;
     std::vector<Piece> pieces;
     std::vector<uint32_t> msz;  // staged bytes of the chunk's packets
     size_t i = 0;
     while (i < count) {
         // Packets [i, j), each packed at a 16-byte boundary, that fit one chunk.
-        uint64_t* h_off = reinterpret_cast<uint64_t*>(S.h_meta);
+        uint64_t* h_off = reinterpret_cast<uint64_t*>(S.h2);
         size_t j = i, pos = 0, bytes = 0;
         pieces.clear();
         msz.clear();
-        while (j < count && j - i < S.mcap) {
+        while (j < count && j - i < max_msgs) {
             const uint32_t m = staged_size(u.pkts + off_of(j), size_of(j));
             if (j > i && pos + up16(m) > limit) break;
             h_off[j - i] = pos;
             msz.push_back(m);
-            if (m) pieces.push_back(Piece{S.h_data + pos, u.pkts + off_of(j), m});
+            if (m) pieces.push_back(Piece{S.h + pos, u.pkts + off_of(j), m});
             pos += up16(m);
             bytes += m;
             ++j;
         }
         const size_t n = j - i;
-        uint32_t* h_size = reinterpret_cast<uint32_t*>(S.h_meta + n * 8);
+        uint32_t* h_size = reinterpret_cast<uint32_t*>(S.h2 + n * 8);
         uint32_t* h_kidx = h_size + n;
         int32_t* h_err = reinterpret_cast<int32_t*>(h_kidx + n);
         uint8_t* h_req = reinterpret_cast<uint8_t*>(h_err + n);
@@ -249,28 +206,28 @@ int rad_host(RadArgs u, bool sign, const KeyTab& kt) {
         parallel_copy(pieces, bytes);
         RadArgs a;
         a.count = n;
-        a.pkts = S.d_data;
-        a.offsets = reinterpret_cast<const uint64_t*>(S.d_meta);
-        a.buf_sizes = reinterpret_cast<const uint32_t*>(S.d_meta + n * 8);
-        a.key_index = u.key_index ? reinterpret_cast<const uint32_t*>(S.d_meta + n * 12) : nullptr;
-        a.errors = reinterpret_cast<int32_t*>(S.d_meta + n * 16);
-        a.req_hdrs = u.req_hdrs ? S.d_meta + n * 20 : nullptr;
-        RAD_TRY(hipMemcpyAsync(S.d_meta, S.h_meta, n * 40, hipMemcpyHostToDevice, S.st));
-        if (pos) RAD_TRY(hipMemcpyAsync(S.d_data, S.h_data, pos, hipMemcpyHostToDevice, S.st));
+        a.pkts = S.d;
+        a.offsets = reinterpret_cast<const uint64_t*>(S.d2);
+        a.buf_sizes = reinterpret_cast<const uint32_t*>(S.d2 + n * 8);
+        a.key_index = u.key_index ? reinterpret_cast<const uint32_t*>(S.d2 + n * 12) : nullptr;
+        a.errors = reinterpret_cast<int32_t*>(S.d2 + n * 16);
+        a.req_hdrs = u.req_hdrs ? S.d2 + n * 20 : nullptr;
+        LCB_HOST_TRY(hipMemcpyAsync(S.d2, S.h2, n * 40, hipMemcpyHostToDevice, S.st));
+        if (pos) LCB_HOST_TRY(hipMemcpyAsync(S.d, S.h, pos, hipMemcpyHostToDevice, S.st));
         if (int rc = rad_enqueue(a, sign, kt, S.st)) {
             (void)hipStreamSynchronize(S.st);
             return rc;
         }
-        RAD_TRY(hipMemcpyAsync(h_err, S.d_meta + n * 16, n * 4, hipMemcpyDeviceToHost, S.st));
-        if (pos) RAD_TRY(hipMemcpyAsync(S.h_data, S.d_data, pos, hipMemcpyDeviceToHost, S.st));
-        RAD_TRY(hipStreamSynchronize(S.st));
+        LCB_HOST_TRY(hipMemcpyAsync(h_err, S.d2 + n * 16, n * 4, hipMemcpyDeviceToHost, S.st));
+        if (pos) LCB_HOST_TRY(hipMemcpyAsync(S.h, S.d, pos, hipMemcpyDeviceToHost, S.st));
+        LCB_HOST_TRY(hipStreamSynchronize(S.st));
         // Only [0, Length) of the packets that may have changed goes back.
         pieces.clear();
         bytes = 0;
         for (size_t k = 0; k < n; ++k) {
             u.errors[i + k] = h_err[k];
             if (h_err[k] == 0 && h_size[k]) {
-                pieces.push_back(Piece{u.pkts + off_of(i + k), S.h_data + h_off[k], h_size[k]});
+                pieces.push_back(Piece{u.pkts + off_of(i + k), S.h + h_off[k], h_size[k]});
                 bytes += h_size[k];
             }
         }

@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import F_DEVICE, HERE, LcbHashError, c_sz, c_u32, c_vp, check, lib
+from ._lib import F_DEVICE, HERE, LcbHashError, c_sz, c_u32, c_vp, check, load_satellite
 from .hash import _is_dev, hash_batch
 
 __all__ = ["verify_batch", "verify_messages", "curve_id", "curve_params", "ecdsa_lib", "CURVES", "ALGO_ECDSA",
@@ -54,19 +54,7 @@ def ecdsa_lib():
     links against); raises LcbHashError if it has not been built."""
     global _elib
     if _elib is None:
-        lib()
-        if not os.path.exists(LIB_PATH):
-            raise LcbHashError(2, "%s is missing: build it with `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C liblcb_amd`)" % LIB_PATH)
-        try:
-            L = ctypes.CDLL(LIB_PATH)
-        except OSError as e:
-            raise LcbHashError(2, "%s does not load: %s" % (LIB_PATH, e))
-        for name, res, args in ECDSA_SIGNATURES:
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _elib = L
+        _elib = load_satellite(LIB_PATH, ECDSA_SIGNATURES)
     return _elib
 
 

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import F_DEVICE, HERE, LcbHashError, c_sz, c_u32, c_u64, c_vp, check, lib
+from ._lib import F_DEVICE, HERE, c_sz, c_u32, c_u64, c_vp, check, load_satellite
 from .hash import _check_extent, _is_dev, _layout
 
 __all__ = ["encrypt_batch", "decrypt_batch", "mac_batch", "sbox", "packed_table", "gost28147_lib",
@@ -59,19 +59,7 @@ def gost28147_lib():
     links against); raises LcbHashError if it has not been built."""
     global _glib
     if _glib is None:
-        lib()
-        if not os.path.exists(LIB_PATH):
-            raise LcbHashError(2, "%s is missing: build it with `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C liblcb_amd`)" % LIB_PATH)
-        try:
-            L = ctypes.CDLL(LIB_PATH)
-        except OSError as e:
-            raise LcbHashError(2, "%s does not load: %s" % (LIB_PATH, e))
-        for name, res, args in GOST28147_SIGNATURES:
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _glib = L
+        _glib = load_satellite(LIB_PATH, GOST28147_SIGNATURES)
     return _glib
 
 

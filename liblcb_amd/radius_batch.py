@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import F_DEVICE, HERE, LcbHashError, c_sz, c_u32, c_u64, c_vp, check, lib
+from ._lib import F_DEVICE, HERE, c_sz, c_u32, c_u64, c_vp, check, load_satellite
 from .hash import _dev_batch, _host_batch, _is_dev, _key_table
 
 __all__ = ["radius_lib", "sign_packed", "verify_packed", "pack", "unpack", "req_headers", "RADIUS_SIGNATURES"]
@@ -41,19 +41,7 @@ def radius_lib():
     links against); raises LcbHashError if it has not been built."""
     global _rlib
     if _rlib is None:
-        lib()
-        if not os.path.exists(LIB_PATH):
-            raise LcbHashError(2, "%s is missing: build it with `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C liblcb_amd`)" % LIB_PATH)
-        try:
-            L = ctypes.CDLL(LIB_PATH)
-        except OSError as e:
-            raise LcbHashError(2, "%s does not load: %s" % (LIB_PATH, e))
-        for name, res, args in RADIUS_SIGNATURES:
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _rlib = L
+        _rlib = load_satellite(LIB_PATH, RADIUS_SIGNATURES)
     return _rlib
 
 

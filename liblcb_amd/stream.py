@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import DIGEST_SIZE, F_DEVICE, HERE, LcbHashError, c_sz, c_u32, c_u64, c_vp, check, lib
+from ._lib import DIGEST_SIZE, F_DEVICE, HERE, c_sz, c_u32, c_u64, c_vp, check, load_satellite
 from .hash import _check_extent, _is_dev, _layout
 
 __all__ = ["StreamSet", "stream_lib", "STATE_DTYPE", "F_KEEP", "STREAM_ABI_VERSION", "STREAM_SIGNATURES"]
@@ -57,19 +57,7 @@ def stream_lib():
     links against); raises LcbHashError if it has not been built."""
     global _slib
     if _slib is None:
-        lib()
-        if not os.path.exists(LIB_PATH):
-            raise LcbHashError(2, "%s is missing: build it with `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C liblcb_amd`)" % LIB_PATH)
-        try:
-            L = ctypes.CDLL(LIB_PATH)
-        except OSError as e:
-            raise LcbHashError(2, "%s does not load: %s" % (LIB_PATH, e))
-        for name, res, args in STREAM_SIGNATURES:
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _slib = L
+        _slib = load_satellite(LIB_PATH, STREAM_SIGNATURES)
     return _slib
 
 
