@@ -199,6 +199,30 @@ def ecdsa_dh_lib():
     return _dhlib
 
 
+ECDSA_KEY_LIB_PATH = os.path.join(HERE, "liblcb_ecdsa_key_gpu.so")
+_KIMP = [c_vp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_u32, c_vp]
+_KEXP = [ctypes.c_int, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_u32, c_vp]
+# every symbol include/lcb_ecdsa_key_gpu.h declares
+ECDSA_KEY_SIGNATURES = [
+    ("lcb_ecdsa_key_import_batch", ctypes.c_int, [ctypes.c_int, ctypes.c_int] + _KIMP),
+    ("lcb_ecdsa_key_export_batch", ctypes.c_int, [ctypes.c_int, ctypes.c_int] + _KEXP),
+    ("ecdsa_pub_key_import_be_batch", ctypes.c_int, [ctypes.c_int] + _KIMP),
+    ("ecdsa_pub_key_import_le_batch", ctypes.c_int, [ctypes.c_int] + _KIMP),
+    ("ecdsa_pub_key_export_be_batch", ctypes.c_int, [ctypes.c_int] + _KEXP),
+    ("ecdsa_pub_key_export_le_batch", ctypes.c_int, [ctypes.c_int] + _KEXP),
+]
+_keylib = None
+
+
+def ecdsa_key_lib():
+    """The loaded liblcb_ecdsa_key_gpu.so (after liblcb_hash_gpu.so, which it
+    links against); raises LcbHashError if it has not been built."""
+    global _keylib
+    if _keylib is None:
+        _keylib = load_satellite(ECDSA_KEY_LIB_PATH, ECDSA_KEY_SIGNATURES)
+    return _keylib
+
+
 def check(rc):
     if rc != 0:
         msg = lib().lcb_hash_strerror(rc).decode()
