@@ -47,7 +47,8 @@
  *
  * Not offered: the compressed, packed and one-byte-infinity key forms and
  * ecdsa_pub_key_import / export_*, key recovery from a signature,
- * ecdsa_verify_priv_key_*, curves of other sizes, a windowed variable-base
+ * ecdsa_verify_priv_key_*, curves of other sizes (the 384- and 512-bit curves
+ * have verification only: lcb_ecdsa_wide_gpu.h), a windowed variable-base
  * multiplication, and any key derivation beyond one digest of the secret
  * (liblcb_amd.ecdsa_dh.dh_digest).
  *
