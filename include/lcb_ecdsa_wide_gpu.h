@@ -47,9 +47,11 @@
  * The digests they pair with are SHA-384 (secp384r1, be), SHA-512
  * (brainpoolP512r1, be) and GOST R 34.11-2012 512 (the tc26 sets, le).
  *
- * Not offered: signing, ECDH, key import and export (the compressed and
- * packed key forms) on these curves; the reference's 320- and 521-bit curves
- * and its curves below 256 bits.
+ * Signing, key generation and public keys from private keys on these curves
+ * are lcb_ecdsa_wide_sign_gpu.h's (liblcb_ecdsa_wide_sign_gpu.so).  Not
+ * offered: ECDH, key import and export (the compressed and packed key forms)
+ * on these curves; the reference's 320- and 521-bit curves and its curves
+ * below 256 bits.
  *
  * Memory modes (flags): LCB_HASH_F_DEVICE (include/lcb_hash_gpu.h) — hashes,
  * sigs, pub_keys, key_idx and status are device pointers and the work is

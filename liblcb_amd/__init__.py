@@ -21,15 +21,18 @@ batched ECDH key agreement (liblcb_amd.ecdsa_dh, its own library
 liblcb_ecdsa_dh_gpu.so), and batched public-key import and export, the
 compressed and packed wire forms (liblcb_amd.ecdsa_key, its own library
 liblcb_ecdsa_key_gpu.so), and the verification again on the 384- and 512-bit
-curves (liblcb_amd.ecdsa_wide, its own library liblcb_ecdsa_wide_gpu.so).
+curves (liblcb_amd.ecdsa_wide, its own library liblcb_ecdsa_wide_gpu.so) and
+signing, key generation and public keys on them (liblcb_amd.ecdsa_wide_sign,
+its own library liblcb_ecdsa_wide_sign_gpu.so).
 """
 from ._lib import (ALG_IDS, ALG_NAMES, BLOCK_SIZE, DIGEST_SIZE, GOST256, GOST512, MD5, SHA1,
                    SHA224, SHA256, SHA384, SHA512, LcbHashError, ecdsa_dh_lib, ecdsa_key_lib, lib)
 from .hash import *  # noqa: F401,F403
-from . import chacha, crc32, ecdsa, ecdsa_dh, ecdsa_key, ecdsa_sign, ecdsa_wide, gost28147, queue, radius, radius_batch, stream  # noqa: F401,E402  (ciphers, CRC-32, ECDSA, ingestion queue, RADIUS, streaming)
+from . import chacha, crc32, ecdsa, ecdsa_dh, ecdsa_key, ecdsa_sign, ecdsa_wide, ecdsa_wide_sign, gost28147, queue, radius, radius_batch, stream  # noqa: F401,E402  (ciphers, CRC-32, ECDSA, ingestion queue, RADIUS, streaming)
 from .ecdsa import ecdsa_lib  # noqa: F401,E402
 from .ecdsa_sign import ecdsa_sign_lib  # noqa: F401,E402
 from .ecdsa_wide import ecdsa_wide_lib  # noqa: F401,E402
+from .ecdsa_wide_sign import ecdsa_wide_sign_lib  # noqa: F401,E402
 from .gost28147 import gost28147_lib  # noqa: F401,E402
 from .radius_batch import radius_lib  # noqa: F401,E402
 from .stream import StreamSet, stream_lib  # noqa: F401,E402
@@ -37,4 +40,5 @@ from .stream import StreamSet, stream_lib  # noqa: F401,E402
 __all__ = ["ALG_IDS", "ALG_NAMES", "BLOCK_SIZE", "DIGEST_SIZE", "MD5", "SHA1", "SHA224",
            "SHA256", "SHA384", "SHA512", "GOST256", "GOST512", "LcbHashError", "lib", "gost28147_lib", "radius_lib",
            "StreamSet", "stream_lib", "ecdsa_lib", "ecdsa_sign", "ecdsa_sign_lib", "ecdsa_dh",
-           "ecdsa_dh_lib", "ecdsa_key", "ecdsa_key_lib", "ecdsa_wide", "ecdsa_wide_lib"]
+           "ecdsa_dh_lib", "ecdsa_key", "ecdsa_key_lib", "ecdsa_wide", "ecdsa_wide_lib",
+           "ecdsa_wide_sign", "ecdsa_wide_sign_lib"]
