@@ -4,8 +4,16 @@
 // multiplication over an odd modulus (serves the field p and the group order
 // n alike), Fermat inversion, Jacobian point arithmetic with every
 // exceptional case, and verify_one(), the whole per-item contract.  The
-// kernel (ecdsa_kernels.hip) calls verify_one() once per lane; the host test
-// (tests/c/ecdsa_verify_host.cpp) calls the same code under the sanitizers.
+// kernels (ecdsa_kernels.hip at 8 limbs, ecdsa_wide_kernels.hip at 12 and 16)
+// call verify_one() once per lane; the host tests
+// (tests/c/ecdsa_verify_host.cpp, tests/c/ecdsa_wide_host.cpp) call the same
+// code under the sanitizers.
+//
+// There is one set of formulas and two multiply-reduces under it.  Everything
+// that multiplies is a template over <L, K>, K a policy type with one static
+// mul(a, b, M): MulCall is the out-of-line body (mont_mul), MulInline the
+// rolled, inlined one (mont_mul_rolled).  DefaultMul<L> picks by limb count,
+// and a call that names no policy gets it.
 //
 // Every array here is indexed with compile-time constants once the limb
 // loops are unrolled: scalar bits are read by shifting the scalar, table
@@ -237,25 +245,106 @@ EC_HD EC_INLINE Num<L> mont_mul(const Num<L>& a, const Num<L>& b, const Mod<L>& 
     return mont_mul_seq<L>(a, b, M, typename MakeSeq<L>::type());
 }
 
+// The same product with no call boundary.  mont_mul_raw is one out-of-line
+// body per translation unit that takes both operands and the modulus by value,
+// 3 L + 1 argument registers.  The device calling convention has 32; at L = 12
+// and L = 16 the rest goes to the stack, which is scratch memory, at every call
+// of the point loop.  mont_mul_rolled is inlined at every site (72 per kernel),
+// and so that each site stays a loop the instruction cache holds, its outer
+// loop over the limbs of b stays rolled.  A rolled loop cannot index a register
+// array by its counter, so b is rotated one limb down per step and the step
+// always reads b.w[0]: L moves beside 2 L multiply-adds.  Resources and
+// timings: DESIGN.md 5k.
+//
+// a b R^-1 mod m for a, b < m: the CIOS steps of mont_mul_raw, one limb of b
+// per trip of a rolled loop.
 template <int L>
-EC_HD EC_INLINE Num<L> to_mont(const Num<L>& a, const Mod<L>& M) {
-    return mont_mul(a, M.rr, M);
+EC_HD EC_INLINE Num<L> mont_mul_rolled(const Num<L>& a, Num<L> b, const Mod<L>& M) {
+    uint32_t t[L + 1];
+    EC_UNROLL
+    for (int j = 0; j < L + 1; ++j) t[j] = 0;
+    EC_NOUNROLL
+    for (int i = 0; i < L; ++i) {
+        const uint32_t bi = b.w[0];
+        EC_UNROLL
+        for (int j = 0; j + 1 < L; ++j) b.w[j] = b.w[j + 1];
+        uint64_t c = 0;
+        EC_UNROLL
+        for (int j = 0; j < L; ++j) {
+            c += (uint64_t)a.w[j] * bi + t[j];
+            t[j] = (uint32_t)c;
+            c >>= 32;
+        }
+        c += t[L];
+        const uint32_t tl = (uint32_t)c, tl1 = (uint32_t)(c >> 32);
+        const uint32_t q = t[0] * M.m0inv;
+        c = (uint64_t)q * M.m.w[0] + t[0];
+        c >>= 32;
+        EC_UNROLL
+        for (int j = 1; j < L; ++j) {
+            c += (uint64_t)q * M.m.w[j] + t[j];
+            t[j - 1] = (uint32_t)c;
+            c >>= 32;
+        }
+        c += tl;
+        t[L - 1] = (uint32_t)c;
+        t[L] = tl1 + (uint32_t)(c >> 32);
+    }
+    Num<L> r, d;
+    EC_UNROLL
+    for (int j = 0; j < L; ++j) r.w[j] = t[j];
+    const uint32_t br = sub_to(d, r, M.m);
+    return select(t[L] != 0 || br == 0, d, r);
 }
 
+// The multiply-reduce as a policy of the formulas below.
+struct MulCall {  // one out-of-line body per translation unit
+    template <int L>
+    static EC_HD EC_INLINE Num<L> mul(const Num<L>& a, const Num<L>& b, const Mod<L>& M) {
+        return mont_mul(a, b, M);
+    }
+};
+// b by value, as mont_mul_rolled takes it: with a reference here and the copy
+// one level down, the 16-limb kernels place their spilled SGPRs differently
+// (DESIGN.md 5k).
+struct MulInline {  // no call boundary, rolled
+    template <int L>
+    static EC_HD EC_INLINE Num<L> mul(const Num<L>& a, Num<L> b, const Mod<L>& M) {
+        return mont_mul_rolled(a, b, M);
+    }
+};
+
+// 8 limbs fit the calling convention; 12 and 16 do not.
 template <int L>
+struct DefaultMulOf {
+    typedef MulInline type;
+};
+template <>
+struct DefaultMulOf<8> {
+    typedef MulCall type;
+};
+template <int L>
+using DefaultMul = typename DefaultMulOf<L>::type;
+
+template <int L, class K = DefaultMul<L>>
+EC_HD EC_INLINE Num<L> to_mont(const Num<L>& a, const Mod<L>& M) {
+    return K::mul(a, M.rr, M);
+}
+
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE Num<L> from_mont(const Num<L>& a, const Mod<L>& M) {
-    return mont_mul(a, small<L>(1), M);
+    return K::mul(a, small<L>(1), M);
 }
 
 // x^-1 in Montgomery form (x^(m-2), m prime); 0 for x = 0.  The exponent is
 // the same in every lane, so its branch does not diverge.
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE Num<L> mont_inv(const Num<L>& x, const Mod<L>& M) {
     Num<L> r = M.one, e = M.exp;
     EC_NOUNROLL
     for (int i = 0; i < 32 * L; ++i) {
-        r = mont_mul(r, r, M);
-        if (shl1(e)) r = mont_mul(r, x, M);
+        r = K::mul(r, r, M);
+        if (shl1(e)) r = K::mul(r, x, M);
     }
     return r;
 }
@@ -265,34 +354,34 @@ EC_HD EC_INLINE Num<L> mont_inv(const Num<L>& x, const Mod<L>& M) {
 // (Y = 0), both of which give Z = 0.  M = 3 X^2 + a Z^4 costs three products
 // for a general a, one for a = 0 and two for a = -3 (3 (X - Z^2) (X + Z^2));
 // a_kind is the same in every lane.
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE Jac<L> jac_dbl(const Jac<L>& P, const Curve<L>& C) {
     const Mod<L>& F = C.p;
-    const Num<L> yy = mont_mul(P.Y, P.Y, F);
-    const Num<L> yyyy = mont_mul(yy, yy, F);
-    Num<L> s = mont_mul(P.X, yy, F);
+    const Num<L> yy = K::mul(P.Y, P.Y, F);
+    const Num<L> yyyy = K::mul(yy, yy, F);
+    Num<L> s = K::mul(P.X, yy, F);
     s = mod_add(s, s, F.m);
     s = mod_add(s, s, F.m);  // 4 X Y^2
     Num<L> m;
     if (C.a_kind == kAMinus3) {
-        const Num<L> zz = mont_mul(P.Z, P.Z, F);
-        m = mont_mul(mod_sub(P.X, zz, F.m), mod_add(P.X, zz, F.m), F);
+        const Num<L> zz = K::mul(P.Z, P.Z, F);
+        m = K::mul(mod_sub(P.X, zz, F.m), mod_add(P.X, zz, F.m), F);
         m = mod_add(mod_add(m, m, F.m), m, F.m);
     } else {
-        const Num<L> xx = mont_mul(P.X, P.X, F);
+        const Num<L> xx = K::mul(P.X, P.X, F);
         m = mod_add(mod_add(xx, xx, F.m), xx, F.m);
         if (C.a_kind != kAZero) {
-            const Num<L> zz = mont_mul(P.Z, P.Z, F);
-            m = mod_add(m, mont_mul(C.a, mont_mul(zz, zz, F), F), F.m);
+            const Num<L> zz = K::mul(P.Z, P.Z, F);
+            m = mod_add(m, K::mul(C.a, K::mul(zz, zz, F), F), F.m);
         }
     }
     Jac<L> R;
-    R.X = mod_sub(mont_mul(m, m, F), mod_add(s, s, F.m), F.m);
+    R.X = mod_sub(K::mul(m, m, F), mod_add(s, s, F.m), F.m);
     Num<L> y8 = mod_add(yyyy, yyyy, F.m);
     y8 = mod_add(y8, y8, F.m);
     y8 = mod_add(y8, y8, F.m);
-    const Num<L> yz = mont_mul(P.Y, P.Z, F);
-    R.Y = mod_sub(mont_mul(m, mod_sub(s, R.X, F.m), F), y8, F.m);
+    const Num<L> yz = K::mul(P.Y, P.Z, F);
+    R.Y = mod_sub(K::mul(m, mod_sub(s, R.X, F.m), F), y8, F.m);
     R.Z = mod_add(yz, yz, F.m);
     return R;
 }
@@ -300,7 +389,7 @@ EC_HD EC_INLINE Jac<L> jac_dbl(const Jac<L>& P, const Curve<L>& C) {
 // P + (x2, y2) for an affine (x2, y2) on the curve (madd).  P = O gives the
 // affine point, P = (x2, y2) the doubling, P = -(x2, y2) the point at
 // infinity.
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE Jac<L> jac_add_affine(const Jac<L>& P, const Num<L>& x2, const Num<L>& y2, const Curve<L>& C) {
     const Mod<L>& F = C.p;
     Jac<L> R;
@@ -310,9 +399,9 @@ EC_HD EC_INLINE Jac<L> jac_add_affine(const Jac<L>& P, const Num<L>& x2, const N
         R.Z = F.one;
         return R;
     }
-    const Num<L> zz = mont_mul(P.Z, P.Z, F);
-    const Num<L> u2 = mont_mul(x2, zz, F);
-    const Num<L> s2 = mont_mul(y2, mont_mul(P.Z, zz, F), F);
+    const Num<L> zz = K::mul(P.Z, P.Z, F);
+    const Num<L> u2 = K::mul(x2, zz, F);
+    const Num<L> s2 = K::mul(y2, K::mul(P.Z, zz, F), F);
     const Num<L> h = mod_sub(u2, P.X, F.m);
     const Num<L> r = mod_sub(s2, P.Y, F.m);
     if (is_zero(h)) {
@@ -320,29 +409,29 @@ EC_HD EC_INLINE Jac<L> jac_add_affine(const Jac<L>& P, const Num<L>& x2, const N
             R.X = x2;
             R.Y = y2;
             R.Z = F.one;
-            return jac_dbl(R, C);
+            return jac_dbl<L, K>(R, C);
         }
         R.X = F.one;
         R.Y = F.one;
         R.Z = small<L>(0);
         return R;
     }
-    const Num<L> hh = mont_mul(h, h, F);
-    const Num<L> hhh = mont_mul(h, hh, F);
-    const Num<L> v = mont_mul(P.X, hh, F);
-    R.X = mod_sub(mod_sub(mont_mul(r, r, F), hhh, F.m), mod_add(v, v, F.m), F.m);
-    R.Y = mod_sub(mont_mul(r, mod_sub(v, R.X, F.m), F), mont_mul(P.Y, hhh, F), F.m);
-    R.Z = mont_mul(P.Z, h, F);
+    const Num<L> hh = K::mul(h, h, F);
+    const Num<L> hhh = K::mul(h, hh, F);
+    const Num<L> v = K::mul(P.X, hh, F);
+    R.X = mod_sub(mod_sub(K::mul(r, r, F), hhh, F.m), mod_add(v, v, F.m), F.m);
+    R.Y = mod_sub(K::mul(r, mod_sub(v, R.X, F.m), F), K::mul(P.Y, hhh, F), F.m);
+    R.Z = K::mul(P.Z, h, F);
     return R;
 }
 
 // Affine x (and y where wanted) of R, Z != 0, as plain numbers below p.
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE void jac_to_affine(const Jac<L>& R, const Mod<L>& F, Num<L>& x, Num<L>* y) {
-    const Num<L> zi = mont_inv(R.Z, F);
-    const Num<L> zi2 = mont_mul(zi, zi, F);
-    x = from_mont(mont_mul(R.X, zi2, F), F);
-    if (y) *y = from_mont(mont_mul(R.Y, mont_mul(zi2, zi, F), F), F);
+    const Num<L> zi = mont_inv<L, K>(R.Z, F);
+    const Num<L> zi2 = K::mul(zi, zi, F);
+    x = from_mont<L, K>(K::mul(R.X, zi2, F), F);
+    if (y) *y = from_mont<L, K>(K::mul(R.Y, K::mul(zi2, zi, F), F), F);
 }
 
 // ------------------------------------------------------------------- import
@@ -381,7 +470,7 @@ EC_HD EC_INLINE void store_num(uint8_t* p, const Num<L>& a, bool le) {
 // What the reference's ecdsa_verify_be / ecdsa_verify_le return for numbers
 // of 4 L bytes (ecdsa.h:1366-1523): the public key check, the range check of
 // r and s, the hash import and its reduction, u1 G + u2 Q, R.x mod n = r.
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE int verify_one(const Curve<L>& C, const uint8_t* hash, uint32_t hash_size, const uint8_t* sig_r,
                                const uint8_t* sig_s, const uint8_t* key_x, const uint8_t* key_y, bool le) {
     const Mod<L>& F = C.p;
@@ -390,11 +479,11 @@ EC_HD EC_INLINE int verify_one(const Curve<L>& C, const uint8_t* hash, uint32_t 
     // has cofactor 1, so n Q = O follows and is not computed.
     const Num<L> qx = load_num<L>(key_x, 4 * L, le), qy = load_num<L>(key_y, 4 * L, le);
     if (geq(qx, F.m) || geq(qy, F.m)) return kBadPoint;
-    const Num<L> x = to_mont(qx, F), y = to_mont(qy, F);
+    const Num<L> x = to_mont<L, K>(qx, F), y = to_mont<L, K>(qy, F);
     {
-        const Num<L> lhs = mont_mul(y, y, F);
-        const Num<L> xxa = mod_add(mont_mul(x, x, F), C.a, F.m);
-        const Num<L> rhs = mod_add(mont_mul(xxa, x, F), C.b, F.m);
+        const Num<L> lhs = K::mul(y, y, F);
+        const Num<L> xxa = mod_add(K::mul(x, x, F), C.a, F.m);
+        const Num<L> rhs = mod_add(K::mul(xxa, x, F), C.b, F.m);
         if (!equal(lhs, rhs)) return kBadPoint;
     }
     const Num<L> r = load_num<L>(sig_r, 4 * L, le), s = load_num<L>(sig_s, 4 * L, le);
@@ -412,14 +501,14 @@ EC_HD EC_INLINE int verify_one(const Curve<L>& C, const uint8_t* hash, uint32_t 
     Num<L> u1, u2;
     if (C.algo == kAlgoEcdsa) {
         if (is_zero(s)) return kEinval;  // no inverse of 0
-        const Num<L> w = mont_inv(to_mont(s, N), N);  // s^-1 R
-        u1 = mont_mul(e, w, N);
-        u2 = mont_mul(r, w, N);
+        const Num<L> w = mont_inv<L, K>(to_mont<L, K>(s, N), N);  // s^-1 R
+        u1 = K::mul(e, w, N);
+        u2 = K::mul(r, w, N);
     } else {
         if (is_zero(e)) e = small<L>(1);
-        const Num<L> w = mont_inv(to_mont(e, N), N);  // e^-1 R
-        u1 = mont_mul(s, w, N);
-        const Num<L> t = mont_mul(r, w, N);
+        const Num<L> w = mont_inv<L, K>(to_mont<L, K>(e, N), N);  // e^-1 R
+        u1 = K::mul(s, w, N);
+        const Num<L> t = K::mul(r, w, N);
         u2 = mod_sub(small<L>(0), t, N.m);  // -(r e^-1)
     }
     // G + Q in affine form for Shamir's trick over {G, Q, G + Q}; it may be a
@@ -428,14 +517,14 @@ EC_HD EC_INLINE int verify_one(const Curve<L>& C, const uint8_t* hash, uint32_t 
     R.X = C.gx;
     R.Y = C.gy;
     R.Z = F.one;
-    R = jac_add_affine(R, x, y, C);
+    R = jac_add_affine<L, K>(R, x, y, C);
     const bool gq_inf = is_zero(R.Z);
     Num<L> gqx, gqy;
     {
-        const Num<L> zi = mont_inv(R.Z, F);
-        const Num<L> zi2 = mont_mul(zi, zi, F);
-        gqx = mont_mul(R.X, zi2, F);
-        gqy = mont_mul(R.Y, mont_mul(zi2, zi, F), F);
+        const Num<L> zi = mont_inv<L, K>(R.Z, F);
+        const Num<L> zi2 = K::mul(zi, zi, F);
+        gqx = K::mul(R.X, zi2, F);
+        gqy = K::mul(R.Y, K::mul(zi2, zi, F), F);
     }
     R.X = F.one;
     R.Y = F.one;
@@ -443,22 +532,22 @@ EC_HD EC_INLINE int verify_one(const Curve<L>& C, const uint8_t* hash, uint32_t 
     EC_NOUNROLL
     for (int i = 0; i < 32 * L; ++i) {
         const bool b1 = shl1(u1) != 0, b2 = shl1(u2) != 0;
-        R = jac_dbl(R, C);
+        R = jac_dbl<L, K>(R, C);
         if ((b1 || b2) && !(b1 && b2 && gq_inf)) {
             const Num<L> tx = select(b2, select(b1, gqx, x), C.gx);
             const Num<L> ty = select(b2, select(b1, gqy, y), C.gy);
-            R = jac_add_affine(R, tx, ty, C);
+            R = jac_add_affine<L, K>(R, tx, ty, C);
         }
     }
     if (is_zero(R.Z)) return kBadPoint;
     // R.x mod n = r without inverting Z: R.x = X / Z^2 < p < 2^(32 L) < 4 n, so
     // R.x mod n = r exactly when X = (r + k n) Z^2 for one k in 0..3 with
     // r + k n < p.  k > 0 is live only where p is well above n.
-    const Num<L> zz = mont_mul(R.Z, R.Z, F);
+    const Num<L> zz = K::mul(R.Z, R.Z, F);
     Num<L> t = r;
     bool live = true, ok = false;
     for (int k = 0; k < 4; ++k) {
-        if (live && !geq(t, F.m)) ok = ok || equal(mont_mul(to_mont(t, F), zz, F), R.X);
+        if (live && !geq(t, F.m)) ok = ok || equal(K::mul(to_mont<L, K>(t, F), zz, F), R.X);
         Num<L> u;
         if (add_to(u, t, N.m)) live = false;  // past 2^(32 L), so past p
         t = u;

@@ -4,36 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ecdsa_sign_args.hpp"
 #include "ecdsa_sign_math.hpp"
 
 namespace lcbec {
 
 typedef BaseTable<kLimbs> Table;
-
-// Device-side description of one signing batch.
-struct SignArgs {
-    const uint8_t* hashes = nullptr;    // count x hash_size
-    const uint8_t* priv = nullptr;      // nkeys x kNumBytes
-    const uint32_t* key_idx = nullptr;  // nullptr: key i for item i
-    const uint8_t* rnd = nullptr;       // count x kNumBytes
-    uint8_t* sigs = nullptr;            // count x 2 kNumBytes: r || s
-    int32_t* status = nullptr;          // count
-    uint64_t count = 0, nkeys = 0;
-    uint32_t hash_size = 0;
-    uint32_t le = 0;
-};
-
-// Key generation (from_rnd: in = rnd, priv is written) and public keys from
-// private keys (in = the private keys, priv = nullptr).
-struct KeyArgs {
-    const uint8_t* in = nullptr;  // count x kNumBytes
-    uint8_t* priv = nullptr;      // count x kNumBytes, or nullptr
-    uint8_t* pub = nullptr;       // count x 2 kNumBytes: x || y
-    int32_t* status = nullptr;    // count
-    uint64_t count = 0;
-    uint32_t from_rnd = 0;
-    uint32_t le = 0;
-};
 
 // The per-curve constant block travels as a kernel argument (scalar loads);
 // `t` is the curve's window table in device memory.

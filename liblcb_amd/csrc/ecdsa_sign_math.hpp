@@ -9,9 +9,12 @@
 //                 8 L mixed additions, no doubling.
 //   sign_one(), keygen_one(), pubkey_one()   the per-item contracts.
 //
-// The kernels (ecdsa_sign_kernels.hip) call these once per lane; the host test
-// (tests/c/ecdsa_sign_host.cpp) calls the same code under the sanitizers, and
-// the host build derives the table (base_table_setup).
+// The kernels (ecdsa_sign_kernels.hip at 8 limbs, ecdsa_wide_sign_kernels.hip
+// at 12 and 16, through ecdsa_sign_items.hpp) call these once per lane; the
+// host tests (tests/c/ecdsa_sign_host.cpp, tests/c/ecdsa_wide_sign_host.cpp)
+// call the same code under the sanitizers, and the host build derives the
+// table (base_table_setup).  K is the multiply-reduce policy of
+// ecdsa_math.hpp.
 //
 // Secrets: no load address depends on the scalar.  Every window reads all 15
 // entries through addresses that are the same in every lane and picks one with
@@ -33,7 +36,8 @@ struct Aff {  // affine, Montgomery form
     Num<L> x, y;
 };
 
-// 8 L windows x 15 entries (L = 8: 960 points, 60 KiB).
+// 8 L windows x 15 entries (L = 8: 960 points, 60 KiB; 135 KiB at 12 limbs,
+// 240 KiB at 16).
 template <int L>
 struct BaseTable {
     Aff<L> t[8 * L][kWinEntries];
@@ -63,7 +67,7 @@ EC_HD EC_INLINE Num<L> bn_mod_reduce(const Num<L>& v, const Num<L>& m) {
 
 // ------------------------------------------------------ fixed-base multiple
 // k G for k < 16^(8 L); the point at infinity (Z = 0) for k = 0.
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE Jac<L> base_mult(const Curve<L>& C, const BaseTable<L>* T, Num<L> k) {
     Jac<L> R;
     R.X = C.p.one;
@@ -83,7 +87,7 @@ EC_HD EC_INLINE Jac<L> base_mult(const Curve<L>& C, const BaseTable<L>* T, Num<L
             tx = select(hit, ent.x, tx);
             ty = select(hit, ent.y, ty);
         }
-        const Jac<L> S = jac_add_affine(R, tx, ty, C);
+        const Jac<L> S = jac_add_affine<L, K>(R, tx, ty, C);
         const bool take = v != 0;  // digit 0: the sum is dropped
         R.X = select(take, S.X, R.X);
         R.Y = select(take, S.Y, R.Y);
@@ -96,7 +100,7 @@ EC_HD EC_INLINE Jac<L> base_mult(const Curve<L>& C, const BaseTable<L>* T, Num<L
 // What the reference's ecdsa_sign_be / ecdsa_sign_le return for numbers of
 // 4 L bytes (ecdsa.h:1192-1351), and on 0 the r and s they export.  r and s
 // are zero on every other status.
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE int sign_one(const Curve<L>& C, const BaseTable<L>* T, const uint8_t* hash, uint32_t hash_size,
                              const uint8_t* priv, const uint8_t* rnd, bool le, Num<L>& r, Num<L>& s) {
     const Mod<L>& N = C.n;
@@ -106,21 +110,21 @@ EC_HD EC_INLINE int sign_one(const Curve<L>& C, const BaseTable<L>* T, const uin
     if (geq(d, N.m)) return kEinval;  // the key check comes first
     const Num<L> k = bn_mod_reduce(load_num<L>(rnd, 4 * L, le), N.m);
     if (is_zero(k)) return kBadPoint;  // k G = O
-    const Jac<L> R = base_mult(C, T, k);
+    const Jac<L> R = base_mult<L, K>(C, T, k);
     if (is_zero(R.Z)) return kBadPoint;
     Num<L> x;
-    jac_to_affine<L>(R, C.p, x, nullptr);
+    jac_to_affine<L, K>(R, C.p, x, nullptr);
     const Num<L> rr = reduce_small(x, N.m, 3);  // x < p < 2^(32 L) < 4 n
     if (is_zero(rr)) return kBadPoint;
     Num<L> e = bn_mod_reduce(load_num<L>(hash, hash_size < 4u * L ? hash_size : 4u * L, le), N.m);
-    const Num<L> rd = mont_mul(to_mont(rr, N), d, N);  // r d
+    const Num<L> rd = K::mul(to_mont<L, K>(rr, N), d, N);  // r d
     Num<L> ss;
     if (C.algo == kAlgoEcdsa) {
-        const Num<L> ki = mont_inv(to_mont(k, N), N);  // k^-1 R
-        ss = mont_mul(ki, mod_add(e, rd, N.m), N);
+        const Num<L> ki = mont_inv<L, K>(to_mont<L, K>(k, N), N);  // k^-1 R
+        ss = K::mul(ki, mod_add(e, rd, N.m), N);
     } else {
         e = select(is_zero(e), small<L>(1), e);
-        ss = mod_add(mont_mul(to_mont(k, N), e, N), rd, N.m);
+        ss = mod_add(K::mul(to_mont<L, K>(k, N), e, N), rd, N.m);
     }
     if (is_zero(ss)) return kBadPoint;
     r = rr;
@@ -133,7 +137,7 @@ EC_HD EC_INLINE int sign_one(const Curve<L>& C, const BaseTable<L>* T, const uin
 // from_rnd = false is ecdsa_recover_pub_key_from_priv_key_be / _le
 // (ecdsa.h:1839-1905): d as given, EINVAL for d >= n.  d = 0 is -1 in both
 // (Q = O is no public key).  d, x, y are zero on every status but 0.
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE int key_one(const Curve<L>& C, const BaseTable<L>* T, const uint8_t* in, bool from_rnd, bool le,
                             Num<L>& d, Num<L>& x, Num<L>& y) {
     const Mod<L>& N = C.n;
@@ -146,24 +150,24 @@ EC_HD EC_INLINE int key_one(const Curve<L>& C, const BaseTable<L>* T, const uint
     else if (geq(v, N.m))
         return kEinval;
     if (is_zero(v)) return kBadPoint;
-    const Jac<L> R = base_mult(C, T, v);
+    const Jac<L> R = base_mult<L, K>(C, T, v);
     if (is_zero(R.Z)) return kBadPoint;
-    jac_to_affine<L>(R, C.p, x, &y);
+    jac_to_affine<L, K>(R, C.p, x, &y);
     d = v;
     return 0;
 }
 
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE int keygen_one(const Curve<L>& C, const BaseTable<L>* T, const uint8_t* rnd, bool le, Num<L>& d,
                                Num<L>& x, Num<L>& y) {
-    return key_one(C, T, rnd, true, le, d, x, y);
+    return key_one<L, K>(C, T, rnd, true, le, d, x, y);
 }
 
-template <int L>
+template <int L, class K = DefaultMul<L>>
 EC_HD EC_INLINE int pubkey_one(const Curve<L>& C, const BaseTable<L>* T, const uint8_t* priv, bool le, Num<L>& x,
                                Num<L>& y) {
     Num<L> d;
-    return key_one(C, T, priv, false, le, d, x, y);
+    return key_one<L, K>(C, T, priv, false, le, d, x, y);
 }
 
 // ------------------------------------------------------- the table (host side)

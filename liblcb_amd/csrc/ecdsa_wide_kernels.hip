@@ -1,14 +1,13 @@
 // ecdsa_wide_kernels.hip — batched ECDSA / GOST R 34.10 signature
 // verification on 384- and 512-bit curves for gfx950
 // (include/lcb_ecdsa_wide_gpu.h).  One lane verifies one signature with
-// wide_verify_one() of ecdsa_wide_math.hpp, one wave per workgroup, one
-// kernel per limb count: no cross-lane traffic, no LDS, no atomics, no
-// scratch.  A lane whose item is rejected early idles under the mask until
-// its wave is done.
+// verify_one() of ecdsa_math.hpp over the inlined multiply-reduce, one wave
+// per workgroup, one kernel per limb count: no cross-lane traffic, no LDS, no
+// atomics, no scratch.  A lane whose item is rejected early idles under the
+// mask until its wave is done.
 #include <hip/hip_runtime.h>
 
 #include "ecdsa_wide_internal.hpp"
-#include "ecdsa_wide_math.hpp"
 
 namespace lcbec {
 
@@ -32,8 +31,8 @@ __device__ __forceinline__ void wide_verify_item(const EcWideArgs& a, const Curv
     }
     const uint8_t* sig = a.sigs + i * (8 * L);
     const uint8_t* key = a.keys + k * (8 * L);
-    a.status[i] =
-        wide_verify_one<L>(c, a.hashes + i * a.hash_size, a.hash_size, sig, sig + 4 * L, key, key + 4 * L, a.le != 0);
+    a.status[i] = verify_one<L, MulInline>(c, a.hashes + i * a.hash_size, a.hash_size, sig, sig + 4 * L, key,
+                                           key + 4 * L, a.le != 0);
 }
 
 __global__ __launch_bounds__(kWideBlock, kWideWavesPerSimd) void ecdsa_wide_verify_kernel_384(

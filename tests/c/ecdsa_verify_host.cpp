@@ -5,7 +5,8 @@
 // Reads lines of hex words on stdin and answers one line each:
 //   C algo p a b Gx Gy n          set the curve (32 big-endian bytes each)
 //                                 -> "C ok m0inv_p one_p rr_p m0inv_n one_n rr_n" | "C bad"
-//   M p|n a b                     -> the Montgomery product a b R^-1 mod m
+//   M p|n a b                     -> the Montgomery product a b R^-1 mod m, two words:
+//                                    MulCall::mul(a, b) and MulInline::mul(a, b)
 //   I p|n a                       -> a^-1 mod m (through to_mont, mont_inv, from_mont)
 //   V le hash_size hash r s Qx Qy -> the status of verify_one
 // Every buffer handed to verify_one is a heap block of exactly its size, so a
@@ -75,7 +76,8 @@ int main() {
             const Mod<L>& M = which == "p" ? C.p : C.n;
             if (op == "M") {
                 in >> b;
-                printf("%s\n", hex_be(mont_mul(num_be(a), num_be(b), M)).c_str());
+                printf("%s %s\n", hex_be(MulCall::mul(num_be(a), num_be(b), M)).c_str(),
+                       hex_be(MulInline::mul(num_be(a), num_be(b), M)).c_str());
             } else {
                 printf("%s\n", hex_be(from_mont(mont_inv(to_mont(num_be(a), M), M), M)).c_str());
             }

@@ -1,14 +1,15 @@
-// ecdsa_wide_host.cpp — liblcb_amd/csrc/ecdsa_wide_math.hpp compiled for the
-// host (tests/test_ecdsa_wide_host.py builds it with AddressSanitizer and
-// UBSan): the same arithmetic and the same wide_verify_one() the kernels run
-// per lane, over the library's own curve table (ecdsa_wide_host.hpp), side by
-// side with verify_one<12> / verify_one<16> of ecdsa_math.hpp.
+// ecdsa_wide_host.cpp — liblcb_amd/csrc/ecdsa_math.hpp at 12 and 16 limbs
+// compiled for the host (tests/test_ecdsa_wide_host.py builds it with
+// AddressSanitizer and UBSan): the same arithmetic and the same
+// verify_one<L, MulInline>() the wide kernels run per lane, over the library's
+// own curve table (ecdsa_wide_host.hpp), side by side with the same formulas
+// over the other multiply-reduce, verify_one<L, MulCall>().
 //
 // Reads lines of hex words on stdin and answers one line each:
 //   K id                             -> "K B m0inv_p one_p rr_p m0inv_n one_n rr_n" | "K bad"
-//   M id p|n a b                     -> wide_mont_mul(a, b) and mont_mul(a, b), two words
-//   I id p|n a                       -> a^-1 mod m through wide_to_mont, wide_mont_inv
-//   V id le hash_size hash r s Qx Qy -> the statuses of wide_verify_one and verify_one, two words
+//   M id p|n a b                     -> MulInline::mul(a, b) and MulCall::mul(a, b), two words
+//   I id p|n a                       -> a^-1 mod m through to_mont, mont_inv over MulInline
+//   V id le hash_size hash r s Qx Qy -> the statuses of verify_one over MulInline and over MulCall, two words
 // Every buffer handed to the verification is a heap block of exactly its
 // size, so a read past hash_size or past a number's B bytes is an error here.
 #include <stdint.h>
@@ -22,7 +23,6 @@
 #include <vector>
 
 #include "../../liblcb_amd/csrc/ecdsa_wide_host.hpp"
-#include "../../liblcb_amd/csrc/ecdsa_wide_math.hpp"
 
 using namespace lcbec;
 
@@ -56,11 +56,11 @@ static int serve(const Curve<L>& C, const std::string& op, std::istringstream& i
         const Mod<L>& M = which == "p" ? C.p : C.n;
         if (op == "M") {
             in >> b;
-            printf("%s %s\n", hex_be(wide_mont_mul(num_be<L>(a), num_be<L>(b), M)).c_str(),
-                   hex_be(mont_mul(num_be<L>(a), num_be<L>(b), M)).c_str());
+            printf("%s %s\n", hex_be(MulInline::mul(num_be<L>(a), num_be<L>(b), M)).c_str(),
+                   hex_be(MulCall::mul(num_be<L>(a), num_be<L>(b), M)).c_str());
         } else {
-            const Num<L> inv = wide_mont_inv(wide_to_mont(num_be<L>(a), M), M);
-            printf("%s\n", hex_be(wide_mont_mul(inv, small<L>(1), M)).c_str());
+            const Num<L> inv = mont_inv<L, MulInline>(to_mont<L, MulInline>(num_be<L>(a), M), M);
+            printf("%s\n", hex_be(MulInline::mul(inv, small<L>(1), M)).c_str());
         }
     } else if (op == "V") {
         int le;
@@ -75,8 +75,8 @@ static int serve(const Curve<L>& C, const std::string& op, std::istringstream& i
         hb.resize(hash_size);
         hb.shrink_to_fit();
         printf("%d %d\n",
-               wide_verify_one(C, hb.data(), hash_size, rb.data(), sb.data(), xb.data(), yb.data(), le != 0),
-               verify_one(C, hb.data(), hash_size, rb.data(), sb.data(), xb.data(), yb.data(), le != 0));
+               verify_one<L, MulInline>(C, hb.data(), hash_size, rb.data(), sb.data(), xb.data(), yb.data(), le != 0),
+               verify_one<L, MulCall>(C, hb.data(), hash_size, rb.data(), sb.data(), xb.data(), yb.data(), le != 0));
     } else {
         return 5;
     }

@@ -1,9 +1,10 @@
-// ecdsa_wide_sign_host.cpp — liblcb_amd/csrc/ecdsa_wide_sign_math.hpp compiled
-// for the host (tests/test_ecdsa_wide_sign_host.py builds it with
-// AddressSanitizer and UBSan): the same table, the same wide_base_mult() and
-// the same wide_sign_one() and wide_key_one() the kernels run per lane, beside
-// sign_one<L>() / key_one<L>() of ecdsa_sign_math.hpp over the other
-// multiply-reduce and wide_verify_one() of ecdsa_wide_math.hpp.
+// ecdsa_wide_sign_host.cpp — liblcb_amd/csrc/ecdsa_sign_math.hpp at 12 and 16
+// limbs compiled for the host (tests/test_ecdsa_wide_sign_host.py builds it
+// with AddressSanitizer and UBSan): the same table, the same base_mult() and
+// the same sign_one<L, MulInline>() and key_one<L, MulInline>() the wide
+// kernels run per lane, beside sign_one<L, MulCall>() / key_one<L, MulCall>(),
+// the same formulas over the other multiply-reduce, and
+// verify_one<L, MulInline>() of ecdsa_math.hpp.
 //
 // Reads lines of hex words on stdin and answers one line each:
 //   C algo p a b Gx Gy n       set the curve (B = 48 or 64 big-endian bytes
@@ -12,10 +13,10 @@
 //   T j v                      -> "x y" of the table entry v 16^j G (v = 1 .. 15),
 //                                 out of Montgomery form, big-endian
 //   S le hash_size hash d rnd  -> "status r s same verify": r, s the B bytes
-//                                 written; same = 1 where sign_one<L> gave the
+//                                 written; same = 1 where MulCall gave the
 //                                 same status and numbers; verify = the status
-//                                 of wide_verify_one for (hash, r, s) under
-//                                 wide_key_one's key of d, or "-" where that
+//                                 of verify_one for (hash, r, s) under
+//                                 key_one's key of d, or "-" where that
 //                                 does not apply (status != 0 or d = 0)
 //   K le rnd                   -> "status d Qx Qy same"
 //   P le d                     -> "status Qx Qy same"
@@ -32,7 +33,7 @@
 #include <string>
 #include <vector>
 
-#include "../../liblcb_amd/csrc/ecdsa_wide_sign_math.hpp"
+#include "../../liblcb_amd/csrc/ecdsa_sign_math.hpp"
 
 using namespace lcbec;
 
@@ -92,25 +93,25 @@ struct Bench {
             in >> j >> v;
             if (j < 0 || j >= 8 * L || v < 1 || v > kWinEntries) return 6;
             const Aff<L>& a = T->t[j][v - 1];
-            printf("%s %s\n", hex_num<L>(wide_from_mont(a.x, C.p), false).c_str(),
-                   hex_num<L>(wide_from_mont(a.y, C.p), false).c_str());
+            printf("%s %s\n", hex_num<L>(from_mont<L, MulInline>(a.x, C.p), false).c_str(),
+                   hex_num<L>(from_mont<L, MulInline>(a.y, C.p), false).c_str());
         } else if (op == "S") {
             uint32_t hash_size;
             std::string h, d, k;
             in >> le >> hash_size >> h >> d >> k;
             const auto hb = exact(h, hash_size), db = exact(d, 4 * L), kb = exact(k, 4 * L);
             Num<L> r, s, r2, s2;
-            const int st = wide_sign_one<L>(C, T.get(), hb.get(), hash_size, db.get(), kb.get(), le != 0, r, s);
-            const int st2 = sign_one<L>(C, T.get(), hb.get(), hash_size, db.get(), kb.get(), le != 0, r2, s2);
+            const int st = sign_one<L, MulInline>(C, T.get(), hb.get(), hash_size, db.get(), kb.get(), le != 0, r, s);
+            const int st2 = sign_one<L, MulCall>(C, T.get(), hb.get(), hash_size, db.get(), kb.get(), le != 0, r2, s2);
             const bool same = st == st2 && equal(r, r2) && equal(s, s2);
             std::string ver = "-";
             if (st == 0) {
                 Num<L> dd, x, y;
-                if (wide_key_one<L>(C, T.get(), db.get(), false, le != 0, dd, x, y) == 0) {
+                if (key_one<L, MulInline>(C, T.get(), db.get(), false, le != 0, dd, x, y) == 0) {
                     const auto rb = bytes_of<L>(r, le != 0), sb = bytes_of<L>(s, le != 0);
                     const auto xb = bytes_of<L>(x, le != 0), yb = bytes_of<L>(y, le != 0);
-                    ver = std::to_string(
-                        wide_verify_one<L>(C, hb.get(), hash_size, rb.get(), sb.get(), xb.get(), yb.get(), le != 0));
+                    ver = std::to_string(verify_one<L, MulInline>(C, hb.get(), hash_size, rb.get(), sb.get(), xb.get(),
+                                                                  yb.get(), le != 0));
                 }
             }
             printf("%d %s %s %d %s\n", st, hex_num<L>(r, le != 0).c_str(), hex_num<L>(s, le != 0).c_str(), (int)same,
@@ -121,8 +122,8 @@ struct Bench {
             in >> le >> k;
             const auto kb = exact(k, 4 * L);
             Num<L> d, x, y, d2, x2, y2;
-            const int st = wide_key_one<L>(C, T.get(), kb.get(), gen, le != 0, d, x, y);
-            const int st2 = key_one<L>(C, T.get(), kb.get(), gen, le != 0, d2, x2, y2);
+            const int st = key_one<L, MulInline>(C, T.get(), kb.get(), gen, le != 0, d, x, y);
+            const int st2 = key_one<L, MulCall>(C, T.get(), kb.get(), gen, le != 0, d2, x2, y2);
             const bool same = st == st2 && equal(d, d2) && equal(x, x2) && equal(y, y2);
             if (gen)
                 printf("%d %s %s %s %d\n", st, hex_num<L>(d, le != 0).c_str(), hex_num<L>(x, le != 0).c_str(),

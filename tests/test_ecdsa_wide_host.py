@@ -1,17 +1,17 @@
 """The wide kernels' arithmetic without a GPU:
-liblcb_amd/csrc/ecdsa_wide_math.hpp compiled for the host as a stand-alone
-program (tests/c/ecdsa_wide_host.cpp) with AddressSanitizer and UBSan, over
+liblcb_amd/csrc/ecdsa_math.hpp at 12 and 16 limbs compiled for the host as a
+stand-alone program (tests/c/ecdsa_wide_host.cpp) with AddressSanitizer and UBSan, over
 the library's own curve table.  Nothing is loaded into Python and nothing is
 preloaded.
 
 1. The Montgomery constants of all twelve moduli (R mod m, R^2 mod m,
    -m^-1 mod 2^32 for p and n of the six curves) equal what Python ints give.
 2. Random Montgomery products and inverses per modulus equal a b R^-1 mod m
-   and a^-1 mod m over Python ints, from the rolled multiply-reduce and from
-   ecdsa_math.hpp's; the operands include 0, 1 and m - 1.
+   and a^-1 mod m over Python ints, from the rolled multiply-reduce (MulInline)
+   and from the out-of-line one (MulCall); the operands include 0, 1 and m - 1.
 3. For every record of tests/golden/ecdsa_wide.json three statuses agree:
-   wide_verify_one(), verify_one<12 | 16>() of the existing header, and the
-   reference's; exactly hash_size / B bytes are read."""
+   verify_one<12 | 16>() over MulInline (the wide kernels'), over MulCall, and
+   the reference's; exactly hash_size / B bytes are read."""
 import os
 import random
 import subprocess

@@ -1,14 +1,14 @@
 """The wide signing kernels' arithmetic without a GPU:
-liblcb_amd/csrc/ecdsa_wide_sign_math.hpp compiled for the host as a stand-alone
-program (tests/c/ecdsa_wide_sign_host.cpp) with AddressSanitizer and UBSan.
+liblcb_amd/csrc/ecdsa_sign_math.hpp at 12 and 16 limbs compiled for the host as
+a stand-alone program (tests/c/ecdsa_wide_sign_host.cpp) with AddressSanitizer and UBSan.
 Nothing is loaded into Python and nothing is preloaded.
 
 1. Every record of tests/golden/ecdsa_wide_sign.json (what the reference
-   returned and wrote) through wide_sign_one() and wide_key_one(): the same
-   status and the same bytes, zeros where the status is not 0; the same again
-   from sign_one<12> / <16> and key_one<12> / <16> of ecdsa_sign_math.hpp over
-   the other multiply-reduce; every status-0 signature with d != 0 accepted by
-   wide_verify_one() under wide_key_one()'s key.
+   returned and wrote) through sign_one<12 | 16>() and key_one<12 | 16>() over
+   MulInline, the wide kernels' multiply-reduce: the same status and the same
+   bytes, zeros where the status is not 0; the same again from the same
+   formulas over MulCall, the other multiply-reduce; every status-0 signature
+   with d != 0 accepted by verify_one() under key_one()'s key.
 2. Window table entries T[j][v] = v 16^j G against Python ints
    (tests/ecdsa_model.mult): the four corners, all of window 0 and of the last
    window, and 64 more per curve."""
@@ -92,7 +92,7 @@ def test_every_fixture_record(exe):
     bad = [(i, g, w) for i, g, w in zip(ids, got, want) if g != w]
     assert not bad, bad[:10]
     assert sum(1 for i in ids if i[2] == "sign") == sum(len(g["sign"]) for g in FX["groups"]) >= 224
-    assert sum(1 for w in want if w.endswith(" 1 0")) > 150  # signatures that went through wide_verify_one
+    assert sum(1 for w in want if w.endswith(" 1 0")) > 150  # signatures that went through verify_one
 
 
 def test_table_entries(exe):
